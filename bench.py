@@ -17,12 +17,20 @@ clients per round, sharded one rank per GPU over RCCL); per-GPU work is
 fixed.  Run under torchrun for N>1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+--dump-outputs DIR additionally writes what the last timed round produced
+(global parameters + sampled clients) as DIR/<name>.npy; inputs and seeds
+are fixed, so two builds can be compared array for array.  --full adds the
+secondary whole-round measurement (train round + sBN statistics pass,
+`round_ms_incl_stats`; null in a plain run).
 """
 import argparse
 import json
 import os
 import time
 
+import numpy as np
 import torch
 
 from heterofl_amd.config import default_config
@@ -50,6 +58,33 @@ def build_cfg(n_gpus, device, dtype):
     return cfg
 
 
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy (float32; integer and
+    float64 tensors as float64).  If the arrays exceed the 64 MB budget in
+    total, each one larger than its equal share is replaced by a fixed,
+    seeded sample of its flattened elements, so two builds stay comparable
+    element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        keep32 = t.is_floating_point() and t.dtype != torch.float64
+        host[name] = t.to(torch.float32 if keep32 else torch.float64).numpy()
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_BUDGET_BYTES // max(len(host), 1)
+    rng = np.random.default_rng(0)
+    for name in sorted(host):
+        a = host[name]
+        if total > DUMP_BUDGET_BYTES and a.nbytes > share:
+            idx = np.sort(rng.choice(a.size, share // a.itemsize,
+                                     replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--gpus', type=int, default=1)
@@ -59,6 +94,15 @@ def main():
                    choices=['float32', 'bfloat16', 'fp8'])
     p.add_argument('--engine', type=str, default='batched',
                    choices=['batched', 'sequential'])
+    p.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                   help='after the timed steps, write the global parameters '
+                        'and the active-user list the last timed round '
+                        'produced as DIR/<name>.npy')
+    p.add_argument('--full', action='store_true',
+                   help='also measure the secondary whole-round figure '
+                        '(train round + sBN statistics pass, '
+                        'round_ms_incl_stats); a plain run times only the '
+                        'headline steps')
     args = p.parse_args()
 
     world_size = int(os.environ.get('WORLD_SIZE', '1'))
@@ -109,8 +153,9 @@ def main():
         runner.train_round(ep)
     sync()
     t0 = time.perf_counter()
+    user_idx = []
     for ep in range(args.warmup + 1, args.warmup + args.steps + 1):
-        runner.train_round(ep)
+        user_idx = runner.train_round(ep)
     sync()
     elapsed = time.perf_counter() - t0
     if dist_ctx is not None:
@@ -118,26 +163,35 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = t.item()
 
-    # secondary whole-round metric: train round + the full-train-set sBN
-    # statistics pass the reference pays every round
+    # what the last timed round handed back: the combined global parameters
+    # and the clients it sampled (every rank finalizes identical values)
+    if args.dump_outputs and rank == 0:
+        arrays = dict(runner.federation.global_parameters)
+        arrays['active_users'] = torch.tensor(user_idx, dtype=torch.int64)
+        dump_outputs(args.dump_outputs, arrays)
+
+    # secondary whole-round metric (--full only): train round + the
+    # full-train-set sBN statistics pass the reference pays every round
     # (src/train_classifier_fed.py:127-138); runs on the native batched
     # engine (runner._native_stats).  Kept outside the headline timed
     # region, reported so the headline cannot be read as end-to-end round
     # wall clock.
-    whole_steps = min(2, args.steps)
-    sync()
-    t1 = time.perf_counter()
-    for ep in range(args.warmup + args.steps + 1,
-                    args.warmup + args.steps + whole_steps + 1):
-        runner.train_round(ep)
-        runner.stats()
-    sync()
-    whole = time.perf_counter() - t1
-    if dist_ctx is not None:
-        t = torch.tensor([whole], device=device if on_gpu else 'cpu')
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        whole = t.item()
-    round_ms_incl_stats = whole / whole_steps * 1000.0
+    round_ms_incl_stats = None
+    if args.full:
+        whole_steps = max(1, min(2, args.steps))
+        sync()
+        t1 = time.perf_counter()
+        for ep in range(args.warmup + args.steps + 1,
+                        args.warmup + args.steps + whole_steps + 1):
+            runner.train_round(ep)
+            runner.stats()
+        sync()
+        whole = time.perf_counter() - t1
+        if dist_ctx is not None:
+            t = torch.tensor([whole], device=device if on_gpu else 'cpu')
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            whole = t.item()
+        round_ms_incl_stats = whole / whole_steps * 1000.0
 
     if os.environ.get('HETEROFL_TIMING') == '1' and rank == 0:
         from heterofl_amd.fed.runner import _phase_timer

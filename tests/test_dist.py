@@ -238,6 +238,9 @@ def test_bench_torchrun_contract(tmp_path):
     assert rec['config']['num_users'] == 200   # weak scaling: 100 users/GPU
     assert rec['config']['active_clients'] == 20
     assert rec['value'] > 0
+    assert rec['ms_per_step'] > 0
+    # a plain run (no --full) skips the whole-round secondary measurement
+    assert rec['round_ms_incl_stats'] is None
 
 
 def _collective_worker(rank, world, port, tmpdir):
