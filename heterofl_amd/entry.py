@@ -465,8 +465,17 @@ def run_fed_eval(cfg, metric_name, result_key='test'):
         logger.safe(True)
         test_model = runner.stats()
         runner.test(test_model, last_epoch - 1)
+        # HETEROFL_EVAL_LEVELS=1 also evaluates every width level a client
+        # may deploy (vision models); without the knob the result file is
+        # unchanged
+        levels = None
+        if os.environ.get('HETEROFL_EVAL_LEVELS', '0') == '1' and \
+                cfg['model_name'] != 'transformer':
+            levels = runner.test_levels(last_epoch - 1)
         logger.safe(False)
         if is_main:
             result = {'cfg': cfg, 'epoch': last_epoch,
                       'logger': {'train': train_logger, 'test': logger}}
+            if levels is not None:
+                result['levels'] = levels
             save(result, './output/result/{}.pt'.format(cfg['model_tag']))

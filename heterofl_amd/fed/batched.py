@@ -515,12 +515,15 @@ class BatchedClientTrainer:
         return self._shard_cache[user]
 
     # model construction ---------------------------------------------------
-    def _batched_model(self, rate, R):
-        key = (rate, R)
+    def _batched_model(self, rate, R, scaler_rate=None):
+        # scaler_rate overrides rate / global_model_rate (per-level
+        # evaluation treats a slice as a full model: Scaler rate 1)
+        key = (rate, R) if scaler_rate is None else (rate, R, scaler_rate)
         if key not in self._model_cache:
             cfg = self.cfg
             name = cfg['model_name']
-            scaler_rate = rate / cfg['global_model_rate']
+            if scaler_rate is None:
+                scaler_rate = rate / cfg['global_model_rate']
             if 'resnet' in name:
                 hidden = [int(np.ceil(rate * h)) for h in cfg['resnet']['hidden_size']]
                 nb, blk = {'resnet18': ([2, 2, 2, 2], BBlock),

@@ -114,10 +114,41 @@ class Federation:
             return [self._split_transformer(u) for u in user_idx]
         raise ValueError('Not valid model name')
 
-    def _scaler_rate(self, user):
-        return self.model_rate[user] / self.cfg['global_model_rate']
+    def _scaler_rate(self, user, rate=None):
+        """Width fraction of the slice: the user's current rate, or an
+        explicit model rate (slice_for_rate)."""
+        if rate is None:
+            rate = self.model_rate[user]
+        return rate / self.cfg['global_model_rate']
 
-    def _split_conv(self, user):
+    def split_for_rate(self, rate):
+        """Index map of the slice a client at `rate` receives."""
+        name = self.cfg['model_name']
+        if name == 'conv':
+            return self._split_conv(None, rate)
+        if 'resnet' in name:
+            return self._split_resnet(None, rate)
+        if name == 'transformer':
+            return self._split_transformer(None, rate)
+        raise ValueError('Not valid model name')
+
+    def slice_for_rate(self, rate):
+        """Global parameters sliced for `rate` — what distribute hands a
+        client fixed at that rate — as a fresh OrderedDict of clones.  Goes
+        through the per-tensor path, never the cached pack buffers of
+        _pack_distribute, so the result aliases neither the global
+        parameters nor a later distribute's output."""
+        pidx = self.split_for_rate(rate)
+        out = OrderedDict()
+        for k, v in self.global_parameters.items():
+            ptype = k.split('.')[-1]
+            if 'weight' in ptype or 'bias' in ptype:
+                out[k] = self._slice_value(v, pidx[k])
+            else:
+                out[k] = v.clone()
+        return out
+
+    def _split_conv(self, user, rate=None):
         """reference: src/fed.py:27-62 — slice output channels of every
         weight with dim>1; the final classifier keeps full rows."""
         gp = self.global_parameters
@@ -125,7 +156,7 @@ class Federation:
         bias_keys = [k for k in gp if 'bias' in k]
         output_weight_name = weight_keys[-1]
         output_bias_name = bias_keys[-1]
-        rate = self._scaler_rate(user)
+        rate = self._scaler_rate(user, rate)
         idx = OrderedDict()
         idx_i = None  # running output axis
         for k, v in gp.items():
@@ -148,11 +179,11 @@ class Federation:
             # non weight/bias keys are skipped (distributed fully)
         return idx
 
-    def _split_resnet(self, user):
+    def _split_resnet(self, user, rate=None):
         """reference: src/fed.py:63-103 — conv1/conv2 sliced; shortcut reuses
         conv1's input index; linear keeps full output rows."""
         gp = self.global_parameters
-        rate = self._scaler_rate(user)
+        rate = self._scaler_rate(user, rate)
         idx = OrderedDict()
         idx_i = None
         for k, v in gp.items():
@@ -186,14 +217,14 @@ class Federation:
                     idx[k] = ParamSlice(idx_i)
         return idx
 
-    def _split_transformer(self, user):
+    def _split_transformer(self, user, rate=None):
         """reference: src/fed.py:104-156 — embedding slices the embedding dim
         keeping full vocab rows; q/k/v slice per head; decoder.linear2 keeps
         full vocab output; idx_i resets to the layer input after linear_q /
         linear_k biases so the residual stream stays at the sliced width."""
         gp = self.global_parameters
         num_heads = self.cfg['transformer']['num_heads']
-        rate = self._scaler_rate(user)
+        rate = self._scaler_rate(user, rate)
         idx = OrderedDict()
         idx_i = None
         for k, v in gp.items():

@@ -192,16 +192,33 @@ class FedRunner:
         weighted all-reduce over RCCL — momentum=None BN keeps the running
         stats as the mean over batches, so the weighted mean over ranks
         reproduces the sequential pass (equal-size batches)."""
+        return self._stats_model(self.cfg['global_model_rate'], None)
+
+    def _stats_model(self, rate, params):
+        """The statistics pass at one width level.  params=None is the
+        global model at the global rate (stats()); otherwise `params` is the
+        global model sliced for `rate` (Federation.slice_for_rate) and the
+        slice is treated as a full model of its own: the tracked model is
+        built with global_model_rate = rate, so its Scaler rate is 1 and the
+        statistics come from the unscaled activations."""
         cfg = self.cfg
         if self.is_lm:
             return self.global_model  # LM path has no sBN pass (reference:
             # src/train_transformer_fed.py:77)
         with torch.no_grad():
-            test_model = make_model(cfg, model_rate=cfg['global_model_rate'],
-                                    track=True).to(cfg['device'])
-            test_model.load_state_dict(self.global_model.state_dict(), strict=False)
+            if params is None:
+                test_model = make_model(
+                    cfg, model_rate=cfg['global_model_rate'],
+                    track=True).to(cfg['device'])
+                test_model.load_state_dict(self.global_model.state_dict(),
+                                           strict=False)
+            else:
+                test_model = make_model(
+                    dict(cfg, global_model_rate=rate), model_rate=rate,
+                    track=True).to(cfg['device'])
+                test_model.load_state_dict(params, strict=False)
             if self._native_stats_ok():
-                self._native_stats(test_model)
+                self._native_stats(test_model, rate, params)
                 return test_model
             test_model.train(True)
             # BN momentum=None is a cumulative average over batches, which is
@@ -270,9 +287,10 @@ class FedRunner:
                 and isinstance(self.trainer, BatchedClientTrainer)
                 and os.environ.get('HETEROFL_NATIVE_STATS', '1') == '1')
 
-    def _native_stats(self, test_model):
+    def _native_stats(self, test_model, rate=None, params=None):
         """Run the full train set (normalized, augmented, unshuffled,
-        batch 500 on GPU) through a 1-group batched model at the global rate
+        batch 500 on GPU) through a 1-group batched model at `rate` (default:
+        the global rate) holding `params` (default: the global parameters)
         and harvest each fused BN kernel's per-batch mean/var into the
         cumulative (momentum=None) running stats of test_model
         (reference semantics: src/train_classifier_fed.py:127-138 with
@@ -285,8 +303,13 @@ class FedRunner:
         cfg = self.cfg
         device = torch.device(cfg['device'])
         trainer = self.trainer
-        bmodel = trainer._batched_model(cfg['global_model_rate'], 1)
-        pack_states(bmodel, [dict(self.federation.global_parameters)])
+        if params is None:
+            bmodel = trainer._batched_model(cfg['global_model_rate'], 1)
+            pack_states(bmodel, [dict(self.federation.global_parameters)])
+        else:
+            # a width level is its own full model: Scaler rate 1
+            bmodel = trainer._batched_model(rate, 1, scaler_rate=1.0)
+            pack_states(bmodel, [dict(params)])
         bmodel.train(True)
 
         state = {}  # module -> [mean, unbiased_var, n_batches]
@@ -377,6 +400,104 @@ class FedRunner:
                 tgt.num_batches_tracked.fill_(k)
         test_model.train(False)
 
+    # ------------------------------------------- per-width-level evaluation
+    def _stage_eval(self):
+        """Raw uint8 test set, labels and the device-side normalizer, staged
+        on the run's device once."""
+        from .batched import DeviceAugment
+        staged = getattr(self, '_eval_staged', None)
+        if staged is None:
+            ds = self.dataset['test']
+            device = torch.device(self.cfg['device'])
+            img = ds.img
+            if img.dim() == 3:
+                img = img.unsqueeze(-1)
+            aug = DeviceAugment(self.cfg['data_name'], device)
+            labels = torch.tensor(ds.target, device=device)
+            staged = (img.to(device), labels, aug)
+            self._eval_staged = staged
+        return staged
+
+    def _native_eval_sums(self, test_model):
+        """(local (U, 3), global (3,)) rows of (loss sum, correct, count) for
+        a tracked model: NativeInference logits over the whole test set, then
+        ops.fused.eval_metrics over the users' CSR shards."""
+        from ..ops.fused import eval_metrics
+        from .infer import NativeInference, batched_logits, user_csr
+        cfg = self.cfg
+        img, labels, aug = self._stage_eval()
+        csr = getattr(self, '_eval_csr', None)
+        if csr is None:
+            csr = user_csr(self.data_split['test'], self.label_split,
+                           cfg['num_users'], cfg['classes_size'],
+                           cfg['mask'], img.device)
+            self._eval_csr = csr
+        scores = batched_logits(NativeInference(test_model), img, aug)
+        return eval_metrics(scores, labels, *csr)
+
+    @staticmethod
+    def _sums_to_metrics(row, flavor, names, suffix=''):
+        """(loss sum, correct, count) -> {'<flavor>-Loss', '<flavor>-Accuracy'}
+        restricted to `names`; None for an empty row."""
+        loss, correct, count = row
+        if count == 0:
+            return None
+        full = {flavor + '-Loss': loss / count,
+                flavor + '-Accuracy': 100.0 * correct / count}
+        return {k + suffix: v for k, v in full.items() if k in names}
+
+    def test_levels(self, epoch):
+        """Evaluate every width level a client may deploy: for each distinct
+        rate in cfg['model_rate'], slice the global parameters, run an sBN
+        statistics pass at that width (the slice is its own full model:
+        Scaler rate 1), and evaluate the tracked slice with the native
+        inference engine.  Returns {rate: {'Global-Loss', 'Global-Accuracy',
+        'Local-Loss', 'Local-Accuracy'}} and logs each metric under
+        'test/<name>@<rate>'; the tracked per-level models stay available in
+        self.level_models.  Vision models only.  Multi-rank: every rank
+        computes the identical result redundantly; rank 0 writes."""
+        from .. import ops as native_ops
+        if self.is_lm:
+            raise NotImplementedError(
+                'test_levels covers the vision models; the transformer has '
+                'no sBN pass and a separate evaluation path')
+        cfg = self.cfg
+        all_names = ['Local-Loss', 'Local-Accuracy', 'Global-Loss',
+                     'Global-Accuracy']
+        out = {}
+        self.level_models = {}
+        with torch.no_grad():
+            for rate in sorted(set(cfg['model_rate']), reverse=True):
+                params = self.federation.slice_for_rate(rate)
+                prev = native_ops.set_large_conv(True)
+                try:
+                    test_model = self._stats_model(rate, params)
+                finally:
+                    native_ops.set_large_conv(prev)
+                test_model.train(False)
+                self.level_models[rate] = test_model
+                local, glob = self._native_eval_sums(test_model)
+                lsum = local.sum(0).tolist()
+                glob = glob.tolist()
+                suffix = '@{}'.format(rate)
+                res = {}
+                for row, flavor in ((glob, 'Global'), (lsum, 'Local')):
+                    ev = self._sums_to_metrics(row, flavor, all_names)
+                    if ev is None:
+                        continue
+                    res.update(ev)
+                    if self.logger:
+                        self.logger.append(
+                            {k + suffix: v for k, v in ev.items()}, 'test',
+                            int(row[2]))
+                out[rate] = res
+        if self.logger and (self.dist_ctx is None or self.dist_ctx.is_main):
+            info = {'info': ['Test Epoch: {}({:.0f}%)'.format(epoch, 100.)]}
+            self.logger.append(info, 'test', mean=False)
+            self.logger.write('test', [n + '@{}'.format(r) for r in out
+                                       for n in all_names])
+        return out
+
     # -------------------------------------------------------- fast GPU eval
     def _fast_vision_eval(self, test_model, metric, logger, cfg, rank, world):
         """Loader-free evaluation: stage the raw uint8 test set on device
@@ -389,19 +510,28 @@ class FedRunner:
         from ..models.functional import masked_cross_entropy
         from .batched import DeviceAugment
         import torch.nn.functional as F
-        ds = self.dataset['test']
         device = torch.device(cfg['device'])
-        staged = getattr(self, '_eval_staged', None)
-        if staged is None:
-            img = ds.img
-            if img.dim() == 3:
-                img = img.unsqueeze(-1)
-            aug = DeviceAugment(cfg['data_name'], device)
-            labels = torch.tensor(ds.target, device=device)
-            staged = (img.to(device), labels, aug)
-            self._eval_staged = staged
-        img, labels, aug = staged
+        img, labels, aug = self._stage_eval()
         n = img.size(0)
+        if os.environ.get('HETEROFL_NATIVE_EVAL', '0') == '1':
+            # native evaluator: hand-written inference kernels for the
+            # logits, one eval_metrics launch pair instead of the per-user
+            # loop.  Every rank holds all sums; it logs its share of users
+            # (and rank 0 the Global row) so logger.sync() merges as usual.
+            local, glob = self._native_eval_sums(test_model)
+            names = cfg['metric_name']['test']
+            local, glob = local.tolist(), glob.tolist()
+            for m in range(rank, cfg['num_users'], world):
+                ev = self._sums_to_metrics(local[m], 'Local',
+                                           names.get('Local', []))
+                if ev is not None and logger:
+                    logger.append(ev, 'test', int(local[m][2]))
+            if rank == 0:
+                ev = self._sums_to_metrics(glob, 'Global',
+                                           names.get('Global', []))
+                if ev is not None and logger:
+                    logger.append(ev, 'test', int(glob[2]))
+            return
         bs = 2048
         scores = []
         for b0 in range(0, n, bs):

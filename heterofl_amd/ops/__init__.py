@@ -78,3 +78,21 @@ def set_fp8(on):
 
 def fp8_enabled():
     return _FP8
+
+
+_LARGE_CONV = os.environ.get('HETEROFL_LARGE_CONV', '0') == '1'
+
+
+def set_large_conv(on):
+    """Send no-grad bf16 groups=1 convs of ops.fused.grouped_conv through the
+    large-batch forward kernel (ops/csrc/conv_infer.hip) where its router
+    admits the shape.  Returns the previous setting.  Env default:
+    HETEROFL_LARGE_CONV (0)."""
+    global _LARGE_CONV
+    prev = _LARGE_CONV
+    _LARGE_CONV = bool(on)
+    return prev
+
+
+def large_conv_enabled():
+    return _LARGE_CONV

@@ -83,6 +83,15 @@ std::vector<at::Tensor> maxpool2_fwd(at::Tensor x);
 void pack_slices(at::Tensor blob, int64_t n, int64_t max_rows);
 at::Tensor maxpool2_bwd(at::Tensor dy, at::Tensor arg, int64_t H,
                         int64_t W);
+at::Tensor conv_pack_weight(at::Tensor w);
+at::Tensor conv_fwd_large(at::Tensor x, at::Tensor packed, at::Tensor bias,
+                          at::Tensor residual, int64_t stride, int64_t pad,
+                          int64_t Cin, int64_t Cout, int64_t k);
+at::Tensor bn_relu_infer(at::Tensor x, at::Tensor scale, at::Tensor shift);
+std::vector<at::Tensor> eval_metrics(at::Tensor scores, at::Tensor labels,
+                                     at::Tensor user_ptr,
+                                     at::Tensor user_samples,
+                                     at::Tensor label_mask);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bn_relu_fwd", &bn_relu_fwd, "fused sBN+ReLU forward");
@@ -129,4 +138,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pack_slices", &pack_slices,
           "one-launch distribute slice pack from a descriptor table");
     m.def("maxpool2_bwd", &maxpool2_bwd, "2x2/2 MaxPool backward");
+    m.def("conv_pack_weight", &conv_pack_weight,
+          "one-time tap-major bf16 repack for conv_fwd_large");
+    m.def("conv_fwd_large", &conv_fwd_large,
+          "large-batch forward conv (bf16, groups=1, packed weight)");
+    m.def("bn_relu_infer", &bn_relu_infer,
+          "eval-mode BN+ReLU from folded scale/shift");
+    m.def("eval_metrics", &eval_metrics,
+          "per-user Local + Global evaluation sums (deterministic)");
 }

@@ -12,7 +12,7 @@ Semantics mirrored from the reference:
 import torch
 import torch.nn.functional as F
 
-from . import require_native, use_native
+from . import require_native, use_native, large_conv_enabled
 
 
 class _FusedNormReLU(torch.autograd.Function):
@@ -160,7 +160,134 @@ class _GroupedConv(torch.autograd.Function):
 
 
 def grouped_conv(x, weight, bias, groups, stride, pad, residual=None):
+    from . import fp8_enabled
+    if large_conv_enabled() and groups == 1 and x.dtype == torch.bfloat16 \
+            and not fp8_enabled() and not (torch.is_grad_enabled() and (
+                x.requires_grad or weight.requires_grad
+                or (bias is not None and bias.requires_grad)
+                or (residual is not None and residual.requires_grad))) \
+            and large_conv_route(x.size(0), weight.size(1), x.size(2),
+                                 x.size(3), weight.size(0), weight.size(2),
+                                 stride, pad):
+        # forward-only large-batch route; the weight is packed per call here
+        # (NativeInference packs once per model instead)
+        return conv_fwd_large(x, conv_pack_weight(weight.detach()),
+                              None if bias is None else bias.detach(),
+                              residual, stride, pad, weight.size(1),
+                              weight.size(0), weight.size(2))
     return _GroupedConv.apply(x, weight, bias, residual, groups, stride, pad)
+
+
+# ------------------------------------------------- large-batch inference ops
+def large_conv_supported(k, stride, pad):
+    """Shapes conv_fwd_large implements: 3x3/pad 1 and 1x1/pad 0, stride 1
+    or 2."""
+    return ((k == 3 and pad == 1) or (k == 1 and pad == 0)) \
+        and stride in (1, 2)
+
+
+def large_conv_route(N, Cin, H, W, Cout, k, stride, pad):
+    """Router: a shape goes to conv_fwd_large only where that kernel
+    measured faster than conv_fwd (profiles/inferbench.txt, both tables).
+    Between the measured shapes a two-line cost model fitted to those tables
+    decides:
+      conv_fwd        ~50 TFLOP/s on its 64-row tile (Cout rounds up to 64);
+      conv_fwd_large  a latency floor of 15 us + 1.2 us per K-slab, and
+                      ~150 TFLOP/s on its padded problem (cin rounds up to
+                      32 per tap, Cout to its 64- or 128-row tile).
+    The model is conservative: every measured shape it routes measured
+    faster on the large kernel; some marginal wins (within ~1.4x) stay on
+    conv_fwd."""
+    if not large_conv_supported(k, stride, pad):
+        return False
+    OH = (H + 2 * pad - k) // stride + 1
+    OW = (W + 2 * pad - k) // stride + 1
+    P = N * OH * OW
+    slabs = k * k * ((Cin + 31) // 32)
+    old_us = 2.0 * P * (-(-Cout // 64) * 64) * Cin * k * k / 50e6
+    cout_pad = 64 if Cout <= 64 else -(-Cout // 128) * 128
+    large_us = max(15.0 + 1.2 * slabs,
+                   2.0 * P * cout_pad * 32 * slabs / 150e6)
+    return old_us > large_us
+
+
+def conv_pack_weight(weight):
+    """One-time tap-major bf16 repack of an (Cout, Cin, k, k) weight for
+    conv_fwd_large."""
+    ext = require_native()
+    return ext.conv_pack_weight(weight.contiguous())
+
+
+def conv_fwd_large(x, packed, bias, residual, stride, pad, Cin, Cout, k):
+    """Forward-only groups=1 conv on bf16 NCHW with a packed weight; bias
+    (fp32) and residual (bf16) are applied in the epilogue."""
+    ext = require_native()
+    return ext.conv_fwd_large(
+        x.contiguous(), packed,
+        bias.float().contiguous() if bias is not None else torch.Tensor(),
+        residual.contiguous() if residual is not None else torch.Tensor(),
+        stride, pad, Cin, Cout, k)
+
+
+def bn_relu_infer(x, scale, shift):
+    """relu(x * scale[c] + shift[c]) — eval-mode BN+ReLU with the running
+    statistics folded into scale/shift (fold_bn).  HIP kernel on GPU, torch
+    on CPU."""
+    if use_native(x):
+        ext = require_native()
+        return ext.bn_relu_infer(x.contiguous(), scale.float().contiguous(),
+                                 shift.float().contiguous())
+    shape = [1, -1] + [1] * (x.dim() - 2)
+    y = x.float() * scale.view(shape) + shift.view(shape)
+    return F.relu(y).to(x.dtype)
+
+
+def fold_bn(weight, bias, mean, var, eps=1e-5):
+    """scale = w*rsqrt(var+eps), shift = b - mean*scale (fp32)."""
+    scale = weight.float() * torch.rsqrt(var.float() + eps)
+    return scale, bias.float() - mean.float() * scale
+
+
+def eval_metrics(scores, labels, user_ptr, user_samples, label_mask):
+    """Per-user Local and the Global evaluation sums from one logit matrix.
+
+    scores (N, C) fp32, labels (N,), users as CSR (user_ptr (U+1,),
+    user_samples (nnz,)), label_mask (U, C) in {0, 1}.  Returns
+    (local (U, 3), global (3,)), each row (loss sum, correct count, sample
+    count).  Local rows use the reference's mask-then-CE order (masked logits
+    are 0, models/functional.py); the Global row uses the raw logits.  The
+    prediction is the lowest index holding the maximum."""
+    scores = scores.float().contiguous()
+    labels = labels.long().contiguous()
+    user_ptr = user_ptr.long().contiguous()
+    user_samples = user_samples.long().contiguous()
+    label_mask = label_mask.float().contiguous()
+    if use_native(scores):
+        ext = require_native()
+        local, glob = ext.eval_metrics(scores, labels, user_ptr, user_samples,
+                                       label_mask)
+        return local, glob
+    U = user_ptr.numel() - 1
+    C = scores.size(1)
+    counts = user_ptr[1:] - user_ptr[:-1]
+    owner = torch.repeat_interleave(torch.arange(U, device=scores.device),
+                                    counts)
+
+    def terms(sc, y):
+        nll = F.cross_entropy(sc, y, reduction='none')
+        mx = sc.max(dim=1, keepdim=True).values
+        cls = torch.arange(C, device=sc.device).expand_as(sc)
+        pred = torch.where(sc == mx, cls, torch.full_like(cls, C)).min(1).values
+        return torch.stack([nll, (pred == y).float(),
+                            torch.ones_like(nll)], 1)
+
+    sc = scores[user_samples].masked_fill(label_mask[owner] == 0, 0)
+    local = torch.zeros(U, 3, dtype=torch.float32, device=scores.device)
+    if owner.numel():
+        local.index_add_(0, owner, terms(sc, labels[user_samples]))
+    glob = terms(scores, labels).sum(0) if scores.size(0) else \
+        torch.zeros(3, device=scores.device)
+    return local, glob
 
 
 class _FusedHead(torch.autograd.Function):
