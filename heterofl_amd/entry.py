@@ -466,12 +466,13 @@ def run_fed_eval(cfg, metric_name, result_key='test'):
         test_model = runner.stats()
         runner.test(test_model, last_epoch - 1)
         # HETEROFL_EVAL_LEVELS=1 also evaluates every width level a client
-        # may deploy (vision models); without the knob the result file is
-        # unchanged
+        # may deploy (test_levels for the vision models, test_lm_levels for
+        # the transformer); without the knob the result file is unchanged
         levels = None
-        if os.environ.get('HETEROFL_EVAL_LEVELS', '0') == '1' and \
-                cfg['model_name'] != 'transformer':
-            levels = runner.test_levels(last_epoch - 1)
+        if os.environ.get('HETEROFL_EVAL_LEVELS', '0') == '1':
+            levels = runner.test_lm_levels(last_epoch - 1) \
+                if cfg['model_name'] == 'transformer' \
+                else runner.test_levels(last_epoch - 1)
         logger.safe(False)
         if is_main:
             result = {'cfg': cfg, 'epoch': last_epoch,

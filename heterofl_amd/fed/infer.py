@@ -18,8 +18,24 @@ The Scaler is the identity at inference (models/modules.py).  On CPU, or
 under HETEROFL_FORCE_EAGER=1, the module itself is called: the CPU path is
 the numerics oracle, as everywhere in this project.
 
-The engine snapshots the model's weights when it is built; rebuild it after
-the model changes.
+NativeLMInference does the same for the masked-LM transformer: per-token NLL
+of pre-masked windows with
+
+    embedding     embed_pos_fwd (token + positional gather)
+    LayerNorm     ln_fwd (R = 1)
+    attention     attn_fwd (S <= 64) / attn_fwd_block (longer windows)
+    residual add  res_drop_fwd (p = 0)
+    GELU          gelu_drop_fwd (p = 0, rate 1)
+    linears       bf16 F.linear on the encoder and decoder.linear1 (the
+                  library-GEMM decision of VERDICT.md K7); linear_q/k/v are
+                  concatenated into one E -> 3E projection
+    head          lm_head_ce (ops/csrc/lm_head_ce.hip): vocabulary projection
+                  fused with the cross-entropy, no (M, V) logits; or the
+                  two-step bf16 F.linear + lm_ce_fwd where the router
+                  (ops.fused.lm_head_route) measured that faster
+
+Both engines snapshot the model's weights when they are built; rebuild them
+after the model changes.
 """
 import torch
 import torch.nn as nn
@@ -27,6 +43,7 @@ import torch.nn as nn
 from .. import ops as native_ops
 from ..models.conv import Conv
 from ..models.resnet import ResNet, Block, Bottleneck
+from ..models.transformer import Transformer
 
 
 class NativeInference:
@@ -194,6 +211,172 @@ class NativeInference:
                 self.head_b if self.head_b is not None else torch.Tensor(),
                 1)[0]
             return scores.squeeze(1)
+
+
+class NativeLMInference:
+    """Per-token NLL of an eager models.transformer.Transformer at inference
+    (Scaler and dropout are the identity).  `head`: 'fused' runs lm_head_ce,
+    'gemm' the two-step bf16 F.linear + lm_ce_fwd, 'auto' follows
+    ops.fused.lm_head_route.  `chunk`: sequences per forward; the default
+    keeps attn_fwd's saved (N*H, S, S) bf16 buffer under ~256 MB."""
+
+    ATTN_BYTES = 256 << 20
+    LOGIT_BYTES = 256 << 20   # logits of one step where they are written
+
+    def __init__(self, model, head='auto', chunk=None):
+        from ..ops.fused import lm_head_pack
+        if not isinstance(model, Transformer):
+            raise TypeError('NativeLMInference supports the transformer only')
+        if head not in ('fused', 'gemm', 'auto'):
+            raise ValueError("head must be 'fused', 'gemm' or 'auto'")
+        self.model = model
+        self.head = head
+        self.chunk = chunk
+        p = next(model.parameters())
+        self.device = p.device
+        self.native = native_ops.use_native(p)
+        emb = model.transformer_embedding
+        self.V = model.num_tokens
+        self.E = emb.embedding.weight.size(1)
+        self.layers = model.transformer_encoder['layers']
+        self.H = self.layers[0].mha.num_heads
+        with torch.no_grad():
+            lin2 = model.decoder.linear2
+            self.packed = lm_head_pack(lin2.weight, lin2.bias)
+            self.head_b = lin2.bias.detach().float().contiguous()
+            if self.native:
+                self.ext = native_ops.require_native()
+                self._snapshot(model)
+
+    # ------------------------------------------------------------- building
+    def _snapshot(self, model):
+        def w16(t):
+            return t.detach().to(torch.bfloat16).contiguous()
+
+        def norm(m):
+            return (m.weight.detach().float().view(1, -1).contiguous(),
+                    m.bias.detach().float().view(1, -1).contiguous(), m.eps)
+
+        def lin(m):
+            return (w16(m.weight), w16(m.bias))
+
+        emb = model.transformer_embedding
+        self.table = w16(emb.embedding.weight).unsqueeze(0)
+        self.pos = w16(emb.positional_embedding.positional_embedding
+                       .weight).unsqueeze(0)
+        self.emb_norm = norm(emb.norm)
+        self.sites = []
+        for layer in self.layers:
+            mha = layer.mha
+            qkv = (mha.linear_q, mha.linear_k, mha.linear_v)
+            self.sites.append({
+                'qkv': (w16(torch.cat([m.weight for m in qkv])),
+                        w16(torch.cat([m.bias for m in qkv]))),
+                'o': lin(mha.linear_o), 'temperature': mha.attention.temperature,
+                'n1': norm(layer.norm1), 'l1': lin(layer.linear1),
+                'l2': lin(layer.linear2), 'n2': norm(layer.norm2)})
+        dec = model.decoder
+        self.dec_l1 = lin(dec.linear1)
+        self.dec_norm = norm(dec.norm1)
+        self.head_w16 = lin(dec.linear2)   # the 'gemm' head
+
+    # -------------------------------------------------------------- running
+    def _chunk(self, S):
+        if self.chunk is not None:
+            return max(int(self.chunk), 1)
+        if not self.native:   # the eager path materialises fp32 logits
+            return max(self.LOGIT_BYTES // (4 * S * self.V), 1)
+        return max(self.ATTN_BYTES // (2 * self.H * S * S), 1)
+
+    def _ln(self, x, site):
+        return self.ext.ln_fwd(x, site[0], site[1], 1, site[2])[0]
+
+    def _hidden(self, src):
+        """(n, S) pre-masked ids -> (n*S, E) bf16 input of the vocabulary
+        head."""
+        import torch.nn.functional as F
+        from ..ops.fused import _rng_cell
+        ext = self.ext
+        n, S = src.shape
+        E, H = self.E, self.H
+        d = E // H
+        seed = _rng_cell(self.device)   # read by the p = 0 kernels, not used
+        x = ext.embed_pos_fwd(src.view(1, n, S).contiguous(), self.table,
+                              self.pos, 1.0)
+        x = self._ln(x.view(n * S, E), self.emb_norm)
+        for st in self.sites:
+            qkv = F.linear(x, *st['qkv']).view(n, S, 3, H, d)
+            qkv = qkv.permute(2, 0, 3, 1, 4).reshape(3, n * H, S, d)
+            attn = ext.attn_fwd if S <= 64 else ext.attn_fwd_block
+            o = attn(qkv[0], qkv[1], qkv[2], st['temperature'])[0]
+            o = o.view(n, H, S, d).permute(0, 2, 1, 3).reshape(n * S, E)
+            o = F.linear(o, *st['o'])
+            x = self._ln(ext.res_drop_fwd(x, o, seed, 0, 1.0, 0.0)[0],
+                         st['n1'])
+            h = ext.gelu_drop_fwd(F.linear(x, *st['l1']), seed, 0, 1.0,
+                                  0.0)[0]
+            h = F.linear(h, *st['l2'])
+            x = self._ln(ext.res_drop_fwd(x, h, seed, 0, 1.0, 0.0)[0],
+                         st['n2'])
+        h = ext.gelu_drop_fwd(F.linear(x, *self.dec_l1), seed, 0, 1.0, 0.0)[0]
+        return self._ln(h, self.dec_norm)
+
+    def _head_nll(self, h, label, vocab_mask):
+        import torch.nn.functional as F
+        from ..ops.fused import lm_head_ce, lm_head_route
+        fused = self.head == 'fused' or (
+            self.head == 'auto' and lm_head_route(h.size(0), self.E, self.V))
+        if fused:
+            return lm_head_ce(h, self.packed, self.head_b, label, vocab_mask,
+                              self.V, self.E)[0]
+        out = []
+        step = max(self.LOGIT_BYTES // (2 * self.V), 1)
+        for r0 in range(0, h.size(0), step):
+            y = label[r0:r0 + step]
+            logits = F.linear(h[r0:r0 + step], *self.head_w16)
+            _, lse = self.ext.lm_ce_fwd(
+                logits, y, vocab_mask if vocab_mask is not None
+                else torch.Tensor(), 1)
+            picked = logits.gather(1, y.view(-1, 1)).squeeze(1).float()
+            if vocab_mask is not None:
+                picked = picked * (vocab_mask[y] != 0)
+            out.append(lse - picked)
+        return torch.cat(out)
+
+    def _eager_hidden(self, src):
+        m = self.model
+        x = m.transformer_embedding(src)
+        for layer in self.layers:
+            x = layer(x)
+        dec = m.decoder
+        x = dec.norm1(dec.activation(dec.scaler(dec.linear1(x))))
+        return x.reshape(-1, x.size(-1))
+
+    def window_nll(self, src, label, vocab_mask=None):
+        """src (N, S) int64 ids with the <mask> id already filled in, label
+        (N, S) int64 -> (N, S) fp32 per-token NLL.  vocab_mask (V,) in
+        {0, 1}: masked logits are 0 and stay in the softmax."""
+        from ..ops.fused import lm_head_ce
+        with torch.no_grad():
+            N, S = src.shape
+            src = src.to(self.device)
+            label = label.to(self.device)
+            if vocab_mask is not None:
+                vocab_mask = vocab_mask.to(self.device).float()
+            out = []
+            step = self._chunk(S)
+            for n0 in range(0, N, step):
+                s = src[n0:n0 + step]
+                y = label[n0:n0 + step].reshape(-1).contiguous()
+                if self.native:
+                    nll = self._head_nll(self._hidden(s), y, vocab_mask)
+                else:
+                    self.model.train(False)
+                    nll = lm_head_ce(self._eager_hidden(s), self.packed,
+                                     self.head_b, y, vocab_mask, self.V,
+                                     self.E)[0]
+                out.append(nll.view(-1, S))
+            return torch.cat(out)
 
 
 # ------------------------------------------------------ evaluation helpers

@@ -498,6 +498,123 @@ class FedRunner:
                                        for n in all_names])
         return out
 
+    # --------------------------------------------------- native LM evaluation
+    def _stage_lm_eval(self):
+        """The batchified test token matrix (rows, T) on the run's device,
+        staged once, and the (start, length) of every BatchDataset(test,
+        bptt) window: full windows plus one shorter tail."""
+        staged = getattr(self, '_lm_eval_staged', None)
+        if staged is None:
+            tokens = self.dataset['test'][:]['label'].to(self.cfg['device'])
+            T, bptt = tokens.size(1), self.cfg['bptt']
+            windows = [(s, min(bptt, T - s)) for s in range(0, T, bptt)]
+            staged = (tokens.contiguous(), windows)
+            self._lm_eval_staged = staged
+        return staged
+
+    def _lm_masked_src(self, tokens):
+        """One Bernoulli(mask_rate) draw over the whole (rows, T) matrix from
+        the global torch RNG; masked positions read the <mask> id."""
+        mask = torch.bernoulli(torch.full(
+            tuple(tokens.shape), self.cfg['mask_rate'], device=tokens.device))
+        return tokens.masked_fill(mask == 1, self.cfg['num_tokens'])
+
+    def _lm_window_metrics(self, model, src, which):
+        """[(loss_w, ppl_w)] for the windows `which`: loss_w is the mean NLL
+        over the window's rows x S_w tokens and ppl_w = exp(loss_w), the
+        reference's per-window Perplexity.  All full windows go through
+        NativeLMInference as one batch of sequences, the tail as another."""
+        from .infer import NativeLMInference
+        tokens, windows = self._stage_lm_eval()
+        engine = NativeLMInference(model)
+        rows, bptt = tokens.size(0), self.cfg['bptt']
+        loss = {}
+        full = [w for w in which if windows[w][1] == bptt]
+        if full:
+            idx = torch.tensor([windows[w][0] for w in full],
+                               device=tokens.device).view(-1, 1) + \
+                torch.arange(bptt, device=tokens.device).view(1, -1)
+            # (windows, rows, bptt) -> one sequence per (window, row)
+            nll = engine.window_nll(
+                src[:, idx].permute(1, 0, 2).reshape(-1, bptt),
+                tokens[:, idx].permute(1, 0, 2).reshape(-1, bptt))
+            means = nll.view(len(full), -1).double().mean(1).tolist()
+            loss.update(zip(full, means))
+        for w in which:
+            if w not in loss:
+                s, n = windows[w]
+                nll = engine.window_nll(src[:, s:s + n].contiguous(),
+                                        tokens[:, s:s + n].contiguous())
+                loss[w] = nll.double().mean().item()
+        return [(loss[w], math.exp(loss[w])) for w in which]
+
+    def _native_lm_test(self, test_model, logger, cfg, rank, world):
+        """LM evaluation under HETEROFL_NATIVE_LM_EVAL=1: this rank's windows
+        (r, r + world, ...) through NativeLMInference, logged per window with
+        weight rows exactly as the eager loop logs them.
+
+        The mask is drawn once per evaluation over the whole token matrix;
+        the eager loop draws one per window, so under mask_rate > 0 the two
+        paths see different (equally distributed) masks and agree only
+        statistically.  With mask_rate == 0 they agree exactly."""
+        tokens, windows = self._stage_lm_eval()
+        src = self._lm_masked_src(tokens)
+        names = cfg['metric_name']['test']['Global']
+        which = list(range(rank, len(windows), world))
+        for loss, ppl in self._lm_window_metrics(test_model, src, which):
+            ev = {'Global-Loss': loss, 'Global-Perplexity': ppl}
+            if logger:
+                logger.append({k: v for k, v in ev.items() if k in names},
+                              'test', tokens.size(0))
+
+    def test_lm_levels(self, epoch):
+        """Masked-LM counterpart of test_levels: for each distinct rate in
+        cfg['model_rate'], descending, slice the global parameters, load the
+        slice into a full model of its own (Scaler rate 1) and evaluate it
+        with NativeLMInference.  One mask, drawn once from the global torch
+        RNG, is shared by every level, so the levels are comparable.
+        Returns {rate: {'Global-Loss', 'Global-Perplexity'}}: the means over
+        the windows of the per-window loss and exp(loss), every window
+        weighing `rows`.  Each metric is logged under 'test/<name>@<rate>';
+        the per-level models stay in self.level_models.  Multi-rank: every
+        rank computes the identical result redundantly; rank 0 writes."""
+        if not self.is_lm:
+            raise NotImplementedError(
+                'test_lm_levels covers the transformer; use test_levels for '
+                'the vision models')
+        cfg = self.cfg
+        all_names = ['Global-Loss', 'Global-Perplexity']
+        out = {}
+        self.level_models = {}
+        with torch.no_grad():
+            tokens, windows = self._stage_lm_eval()
+            src = self._lm_masked_src(tokens)
+            which = list(range(len(windows)))
+            for rate in sorted(set(cfg['model_rate']), reverse=True):
+                params = self.federation.slice_for_rate(rate)
+                model = make_model(dict(cfg, global_model_rate=rate),
+                                   model_rate=rate).to(cfg['device'])
+                model.load_state_dict(params)
+                model.train(False)
+                self.level_models[rate] = model
+                res = self._lm_window_metrics(model, src, which)
+                suffix = '@{}'.format(rate)
+                for loss, ppl in res:
+                    if self.logger:
+                        self.logger.append(
+                            {'Global-Loss' + suffix: loss,
+                             'Global-Perplexity' + suffix: ppl}, 'test',
+                            tokens.size(0))
+                out[rate] = {
+                    'Global-Loss': sum(r[0] for r in res) / len(res),
+                    'Global-Perplexity': sum(r[1] for r in res) / len(res)}
+        if self.logger and (self.dist_ctx is None or self.dist_ctx.is_main):
+            info = {'info': ['Test Epoch: {}({:.0f}%)'.format(epoch, 100.)]}
+            self.logger.append(info, 'test', mean=False)
+            self.logger.write('test', [n + '@{}'.format(r) for r in out
+                                       for n in all_names])
+        return out
+
     # -------------------------------------------------------- fast GPU eval
     def _fast_vision_eval(self, test_model, metric, logger, cfg, rank, world):
         """Loader-free evaluation: stage the raw uint8 test set on device
@@ -580,7 +697,11 @@ class FedRunner:
         user and the Global set by sample across ranks; logger.sync() then
         merges the shards' weighted sums so every rank sees the sequential
         run's exact means (weighted means are additive over disjoint
-        shards)."""
+        shards).
+
+        The transformer is evaluated by the eager per-window loop, or under
+        HETEROFL_NATIVE_LM_EVAL=1 by NativeLMInference (_native_lm_test,
+        which also documents how its token mask differs)."""
         cfg = self.cfg
         if torch.cuda.is_available() and not self.is_lm:
             cfg = dict(cfg)
@@ -626,6 +747,8 @@ class FedRunner:
                                          input, output)
                     if logger:
                         logger.append(ev, 'test', input_size)
+            elif os.environ.get('HETEROFL_NATIVE_LM_EVAL', '0') == '1':
+                self._native_lm_test(test_model, logger, cfg, rank, world)
             else:
                 ds = BatchDataset(self.dataset['test'], cfg['bptt'])
                 for i in range(rank, len(ds), world):

@@ -92,6 +92,11 @@ std::vector<at::Tensor> eval_metrics(at::Tensor scores, at::Tensor labels,
                                      at::Tensor user_ptr,
                                      at::Tensor user_samples,
                                      at::Tensor label_mask);
+at::Tensor lm_head_pack(at::Tensor w);
+std::vector<at::Tensor> lm_head_ce(at::Tensor x, at::Tensor packed,
+                                   at::Tensor bias, at::Tensor labels,
+                                   at::Tensor vocab_mask, int64_t V,
+                                   int64_t E, int64_t splits);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bn_relu_fwd", &bn_relu_fwd, "fused sBN+ReLU forward");
@@ -146,4 +151,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "eval-mode BN+ReLU from folded scale/shift");
     m.def("eval_metrics", &eval_metrics,
           "per-user Local + Global evaluation sums (deterministic)");
+    m.def("lm_head_pack", &lm_head_pack,
+          "one-time padded bf16 repack of the LM vocabulary head");
+    m.def("lm_head_ce", &lm_head_ce,
+          "fused vocabulary projection + cross-entropy (no logits written)");
 }

@@ -290,6 +290,74 @@ def eval_metrics(scores, labels, user_ptr, user_samples, label_mask):
     return local, glob
 
 
+# ------------------------------------------------ LM evaluation head (K7/K10)
+LM_HEAD_KPAD = 32   # E padding of the packed head (MFMA K)
+LM_HEAD_VPAD = 64   # V padding of the packed head (column tile)
+
+
+def lm_head_pack(weight, bias=None):
+    """One-time repack of the decoder's vocabulary projection (V, E) for
+    lm_head_ce: E zero-padded to a multiple of 32, V to a multiple of 64.
+    bf16 from the HIP kernel on GPU; on CPU the same layout in fp32 (the
+    oracle path does not round).  `bias` is only checked against V: it stays
+    fp32 and is handed to lm_head_ce as it is."""
+    V, E = weight.shape
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise ValueError('lm_head_pack: bias must be (V,)')
+    if not 1 <= E <= 256:
+        raise ValueError('lm_head_pack: 1 <= E <= 256')
+    if use_native(weight):
+        ext = require_native()
+        return ext.lm_head_pack(weight.detach().float().contiguous())
+    Vp = -(-V // LM_HEAD_VPAD) * LM_HEAD_VPAD
+    Ep = -(-E // LM_HEAD_KPAD) * LM_HEAD_KPAD
+    out = torch.zeros(Vp, Ep, dtype=torch.float32, device=weight.device)
+    out[:V, :E] = weight.detach().float()
+    return out
+
+
+def lm_head_ce(x, packed, bias, labels, vocab_mask, V, E, splits=0):
+    """Vocabulary projection fused with cross-entropy: x (M, E), packed from
+    lm_head_pack, bias (V,) fp32 or None, labels (M,) int64 in [0, V),
+    vocab_mask (V,) fp32 or None -> (row_nll (M,), row_lse (M,)) fp32.
+
+    logit = x . W^T + b in fp32; a vocab-masked column's logit is exactly 0
+    (bias included) and still takes part in the softmax, as in
+    models/functional.py; the (M, V) logits are never written on the GPU
+    path (ops/csrc/lm_head_ce.hip, bf16 x).  `splits` cuts the vocabulary
+    over that many blocks per row tile (0: the host fills the GPU); for a
+    given value the result is bit-reproducible."""
+    if use_native(x):
+        ext = require_native()
+        none = torch.Tensor()
+        nll, lse = ext.lm_head_ce(
+            x.contiguous(), packed,
+            bias.float().contiguous() if bias is not None else none,
+            labels.long().contiguous(),
+            vocab_mask.float().contiguous() if vocab_mask is not None
+            else none, V, E, splits)
+        return nll, lse
+    logits = x.float() @ packed[:V, :E].float().t()
+    if bias is not None:
+        logits = logits + bias.float()
+    if vocab_mask is not None:
+        logits = logits.masked_fill(vocab_mask.view(1, V) == 0, 0)
+    lse = torch.logsumexp(logits, dim=1)
+    return lse - logits.gather(1, labels.long().view(-1, 1)).squeeze(1), lse
+
+
+def lm_head_route(M, E, V):
+    """Router of NativeLMInference(head='auto'): True sends the head to
+    lm_head_ce, False to the two-step bf16 F.linear + lm_ce_fwd.  The sweep
+    in profiles/lm_inferbench.txt (V = 33278, E in {256, 64, 16}, M in {640,
+    32768}) measured the fused kernel at 0.16x - 0.64x of the two-step time
+    at every point, so that envelope is routed: at least one full window of
+    rows and at least the WikiText2 vocabulary (more rows or more columns
+    only lengthen the loops the kernel amortises its prologue over).
+    Smaller problems were not measured and stay on the two-step head."""
+    return M >= 640 and V >= 33278 and E <= 256
+
+
 class _FusedHead(torch.autograd.Function):
     """AdaptiveAvgPool(1) + flatten + per-client Linear in one kernel each
     way (ops/csrc/head.hip).  scores come back fp32 (they feed masked-CE)."""
