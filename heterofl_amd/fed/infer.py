@@ -33,6 +33,12 @@ of pre-masked windows with
                   fused with the cross-entropy, no (M, V) logits; or the
                   two-step bf16 F.linear + lm_ce_fwd where the router
                   (ops.fused.lm_head_route) measured that faster
+    fill-mask     lm_head_topk (ops/csrc/lm_head_topk.hip): window_topk and
+                  fill_mask take every position's k <= 8 most likely tokens,
+                  their log-probabilities and the label's NLL from one
+                  vocabulary pass, again without (M, V) logits; it is the
+                  only route (no two-step top-k measured faster, see
+                  profiles/NOTES.md)
 
 Both engines snapshot the model's weights when they are built; rebuild them
 after the model changes.
@@ -214,8 +220,9 @@ class NativeInference:
 
 
 class NativeLMInference:
-    """Per-token NLL of an eager models.transformer.Transformer at inference
-    (Scaler and dropout are the identity).  `head`: 'fused' runs lm_head_ce,
+    """Per-token NLL (window_nll) and top-k predictions (window_topk,
+    fill_mask) of an eager models.transformer.Transformer at inference
+    (Scaler and dropout are the identity).  `head` (window_nll only): 'fused' runs lm_head_ce,
     'gemm' the two-step bf16 F.linear + lm_ce_fwd, 'auto' follows
     ops.fused.lm_head_route.  `chunk`: sequences per forward; the default
     keeps attn_fwd's saved (N*H, S, S) bf16 buffer under ~256 MB."""
@@ -377,6 +384,79 @@ class NativeLMInference:
                                      self.E)[0]
                 out.append(nll.view(-1, S))
             return torch.cat(out)
+
+    def window_topk(self, src, k=5, label=None, vocab_mask=None,
+                    only_masked=False):
+        """src (N, S) int64 ids with the <mask> id already filled in ->
+        (ids (N, S, k) int64, logp (N, S, k) fp32, nll (N, S) fp32 or None
+        without `label`): every position's k most likely tokens in
+        descending order (equal logits: the lower id first), their
+        log-probabilities logit - lse, and the label's NLL from the same
+        vocabulary pass (lm_head_topk).  only_masked: the head runs on the
+        positions where src is the <mask> id only; every other position
+        reads ids -1, logp -inf, nll 0."""
+        from ..ops.fused import lm_head_topk
+        with torch.no_grad():
+            N, S = src.shape
+            src = src.to(self.device)
+            if label is not None:
+                label = label.to(self.device)
+            if vocab_mask is not None:
+                vocab_mask = vocab_mask.to(self.device).float()
+            ids, logp, nll = [], [], []
+            step = self._chunk(S)
+            for n0 in range(0, N, step):
+                s = src[n0:n0 + step]
+                rows = s.numel()
+                if self.native:
+                    h = self._hidden(s)
+                else:
+                    self.model.train(False)
+                    h = self._eager_hidden(s)
+                y = None if label is None else \
+                    label[n0:n0 + step].reshape(-1).contiguous()
+                # the split count of the chunk's full row count, also where
+                # only the masked rows run: the two modes then agree bit
+                # for bit on those rows
+                splits = self.ext.lm_head_topk_splits(rows, self.V) \
+                    if self.native else 0
+                if only_masked:
+                    at = (s.reshape(-1) == self.V).nonzero().squeeze(1)
+                    h = h[at].contiguous()
+                    y = None if y is None else y[at].contiguous()
+                i_c = torch.full((rows, k), -1, dtype=torch.long,
+                                 device=self.device)
+                p_c = torch.full((rows, k), float('-inf'),
+                                 dtype=torch.float32, device=self.device)
+                n_c = torch.zeros(rows, dtype=torch.float32,
+                                  device=self.device)
+                if h.size(0):
+                    val, idx, lse, nl = lm_head_topk(
+                        h, self.packed, self.head_b, y, vocab_mask, self.V,
+                        self.E, k, splits)
+                    lp = val - lse.view(-1, 1)
+                    if only_masked:
+                        i_c[at], p_c[at] = idx, lp
+                        if y is not None:
+                            n_c[at] = nl
+                    else:
+                        i_c, p_c = idx, lp
+                        n_c = nl if y is not None else n_c
+                ids.append(i_c.view(-1, S, k))
+                logp.append(p_c.view(-1, S, k))
+                nll.append(n_c.view(-1, S))
+            return (torch.cat(ids), torch.cat(logp),
+                    None if label is None else torch.cat(nll))
+
+    def fill_mask(self, src, k=5, vocab_mask=None):
+        """Predictions for the <mask> positions of src (N, S): (positions
+        (P, 2) int64 [sequence, offset] in row-major order, ids (P, k)
+        int64, probs (P, k) fp32 = exp(logp))."""
+        ids, logp, _ = self.window_topk(src, k=k, vocab_mask=vocab_mask,
+                                        only_masked=True)
+        pos = (src.to(self.device) == self.V).nonzero()
+        return (pos, ids[pos[:, 0], pos[:, 1]],
+                logp[pos[:, 0], pos[:, 1]].exp())
 
 
 # ------------------------------------------------------ evaluation helpers

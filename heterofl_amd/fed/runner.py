@@ -519,39 +519,110 @@ class FedRunner:
             tuple(tokens.shape), self.cfg['mask_rate'], device=tokens.device))
         return tokens.masked_fill(mask == 1, self.cfg['num_tokens'])
 
-    def _lm_window_metrics(self, model, src, which):
+    @staticmethod
+    def _lm_topk():
+        """HETEROFL_LM_TOPK: 0 / unset is off, 1..8 asks the LM evaluation
+        for top-1 / top-k token accuracy next to loss and perplexity."""
+        raw = os.environ.get('HETEROFL_LM_TOPK', '0')
+        try:
+            k = int(raw)
+        except ValueError:
+            k = -1
+        if not 0 <= k <= 8:
+            raise ValueError('HETEROFL_LM_TOPK must be an integer in 0..8, '
+                             'got {!r}'.format(raw))
+        return k
+
+    def _lm_window_metrics(self, model, src, which, topk=0):
         """[(loss_w, ppl_w)] for the windows `which`: loss_w is the mean NLL
         over the window's rows x S_w tokens and ppl_w = exp(loss_w), the
         reference's per-window Perplexity.  All full windows go through
-        NativeLMInference as one batch of sequences, the tail as another."""
+        NativeLMInference as one batch of sequences, the tail as another.
+
+        topk > 0: the NLL comes from window_topk (one vocabulary pass for
+        loss and predictions) and every tuple gains a third entry, the
+        window's integer counts {'n', 'hit1', 'hitk', 'mn', 'mhit1',
+        'mhitk'}: positions, labels met by the first / by any of the topk
+        predictions, and the same over the <mask> positions of src."""
         from .infer import NativeLMInference
         tokens, windows = self._stage_lm_eval()
         engine = NativeLMInference(model)
         rows, bptt = tokens.size(0), self.cfg['bptt']
-        loss = {}
+        loss, counts = {}, {}
+
+        def means(nll, groups):
+            # one mean per window of the batch of full windows; the tail
+            # (groups 0) is reduced as a whole
+            if not groups:
+                return [nll.double().mean().item()]
+            return nll.view(groups, -1).double().mean(1).tolist()
+
+        def run(s, y, groups):
+            """Mean NLL and, with topk, the 6 counts of each of `groups`
+            windows (0: the tail, one window)."""
+            if not topk:
+                return means(engine.window_nll(s, y), groups), None
+            ids, _, nll = engine.window_topk(s, k=topk, label=y)
+            hit = ids == y.unsqueeze(-1)
+            hit1, hitk = hit[..., 0], hit.any(-1)
+            masked = s == self.cfg['num_tokens']
+            cnt = torch.stack([torch.ones_like(hit1), hit1, hitk, masked,
+                               hit1 & masked, hitk & masked], -1)
+            return means(nll, groups), \
+                cnt.view(max(groups, 1), -1, 6).sum(1).tolist()
+
         full = [w for w in which if windows[w][1] == bptt]
         if full:
             idx = torch.tensor([windows[w][0] for w in full],
                                device=tokens.device).view(-1, 1) + \
                 torch.arange(bptt, device=tokens.device).view(1, -1)
             # (windows, rows, bptt) -> one sequence per (window, row)
-            nll = engine.window_nll(
-                src[:, idx].permute(1, 0, 2).reshape(-1, bptt),
-                tokens[:, idx].permute(1, 0, 2).reshape(-1, bptt))
-            means = nll.view(len(full), -1).double().mean(1).tolist()
-            loss.update(zip(full, means))
+            mean, cnt = run(src[:, idx].permute(1, 0, 2).reshape(-1, bptt),
+                            tokens[:, idx].permute(1, 0, 2)
+                            .reshape(-1, bptt), len(full))
+            loss.update(zip(full, mean))
+            if topk:
+                counts.update(zip(full, cnt))
         for w in which:
             if w not in loss:
                 s, n = windows[w]
-                nll = engine.window_nll(src[:, s:s + n].contiguous(),
-                                        tokens[:, s:s + n].contiguous())
-                loss[w] = nll.double().mean().item()
-        return [(loss[w], math.exp(loss[w])) for w in which]
+                mean, cnt = run(src[:, s:s + n].contiguous(),
+                                tokens[:, s:s + n].contiguous(), 0)
+                loss[w] = mean[0]
+                if topk:
+                    counts[w] = cnt[0]
+        if not topk:
+            return [(loss[w], math.exp(loss[w])) for w in which]
+        keys = ('n', 'hit1', 'hitk', 'mn', 'mhit1', 'mhitk')
+        return [(loss[w], math.exp(loss[w]), dict(zip(keys, counts[w])))
+                for w in which]
+
+    @staticmethod
+    def _lm_accuracy_names(topk):
+        """(all-position names, masked-position names) under the knob."""
+        tail = ['-Top{}'.format(topk)] if topk > 1 else []
+        return (['Global-Accuracy' + t for t in [''] + tail],
+                ['Global-Masked-Accuracy' + t for t in [''] + tail])
+
+    def _lm_log_accuracy(self, logger, cnt, topk, rows, suffix=''):
+        """Log one window's accuracies (percent): over all positions with
+        weight `rows`, like the loss; over the <mask> positions with weight
+        their number, which pools them over the evaluation."""
+        names, mnames = self._lm_accuracy_names(topk)
+        hits = (cnt['hit1'], cnt['hitk'])
+        logger.append({n + suffix: 100.0 * h / cnt['n']
+                       for n, h in zip(names, hits)}, 'test', rows)
+        if cnt['mn']:
+            mhits = (cnt['mhit1'], cnt['mhitk'])
+            logger.append({n + suffix: 100.0 * h / cnt['mn']
+                           for n, h in zip(mnames, mhits)}, 'test', cnt['mn'])
 
     def _native_lm_test(self, test_model, logger, cfg, rank, world):
         """LM evaluation under HETEROFL_NATIVE_LM_EVAL=1: this rank's windows
         (r, r + world, ...) through NativeLMInference, logged per window with
-        weight rows exactly as the eager loop logs them.
+        weight rows exactly as the eager loop logs them.  HETEROFL_LM_TOPK=k
+        adds Global-Accuracy[-Top{k}] and Global-Masked-Accuracy[-Top{k}]
+        (see test_lm_levels).
 
         The mask is drawn once per evaluation over the whole token matrix;
         the eager loop draws one per window, so under mask_rate > 0 the two
@@ -559,13 +630,17 @@ class FedRunner:
         statistically.  With mask_rate == 0 they agree exactly."""
         tokens, windows = self._stage_lm_eval()
         src = self._lm_masked_src(tokens)
+        topk = self._lm_topk()
         names = cfg['metric_name']['test']['Global']
         which = list(range(rank, len(windows), world))
-        for loss, ppl in self._lm_window_metrics(test_model, src, which):
-            ev = {'Global-Loss': loss, 'Global-Perplexity': ppl}
+        for res in self._lm_window_metrics(test_model, src, which, topk):
+            ev = {'Global-Loss': res[0], 'Global-Perplexity': res[1]}
             if logger:
                 logger.append({k: v for k, v in ev.items() if k in names},
                               'test', tokens.size(0))
+                if topk:
+                    self._lm_log_accuracy(logger, res[2], topk,
+                                          tokens.size(0))
 
     def test_lm_levels(self, epoch):
         """Masked-LM counterpart of test_levels: for each distinct rate in
@@ -577,13 +652,22 @@ class FedRunner:
         the windows of the per-window loss and exp(loss), every window
         weighing `rows`.  Each metric is logged under 'test/<name>@<rate>';
         the per-level models stay in self.level_models.  Multi-rank: every
-        rank computes the identical result redundantly; rank 0 writes."""
+        rank computes the identical result redundantly; rank 0 writes.
+
+        HETEROFL_LM_TOPK=k (1..8) adds token accuracy in percent, from the
+        same vocabulary pass as the loss: 'Global-Accuracy' and, for k > 1,
+        'Global-Accuracy-Top{k}' (label among the first / the first k
+        predictions, averaged over the windows like the loss), and
+        'Global-Masked-Accuracy[-Top{k}]' (the same over the <mask>
+        positions, pooled over the evaluation; left out when nothing is
+        masked)."""
         if not self.is_lm:
             raise NotImplementedError(
                 'test_lm_levels covers the transformer; use test_levels for '
                 'the vision models')
         cfg = self.cfg
-        all_names = ['Global-Loss', 'Global-Perplexity']
+        topk = self._lm_topk()
+        names, mnames = self._lm_accuracy_names(topk) if topk else ([], [])
         out = {}
         self.level_models = {}
         with torch.no_grad():
@@ -597,22 +681,34 @@ class FedRunner:
                 model.load_state_dict(params)
                 model.train(False)
                 self.level_models[rate] = model
-                res = self._lm_window_metrics(model, src, which)
+                res = self._lm_window_metrics(model, src, which, topk)
                 suffix = '@{}'.format(rate)
-                for loss, ppl in res:
+                for r in res:
                     if self.logger:
                         self.logger.append(
-                            {'Global-Loss' + suffix: loss,
-                             'Global-Perplexity' + suffix: ppl}, 'test',
+                            {'Global-Loss' + suffix: r[0],
+                             'Global-Perplexity' + suffix: r[1]}, 'test',
                             tokens.size(0))
+                        if topk:
+                            self._lm_log_accuracy(self.logger, r[2], topk,
+                                                  tokens.size(0), suffix)
                 out[rate] = {
                     'Global-Loss': sum(r[0] for r in res) / len(res),
                     'Global-Perplexity': sum(r[1] for r in res) / len(res)}
+                if topk:
+                    for n, h in zip(names, ('hit1', 'hitk')):
+                        out[rate][n] = sum(100.0 * r[2][h] / r[2]['n']
+                                           for r in res) / len(res)
+                    mn = sum(r[2]['mn'] for r in res)
+                    for n, h in zip(mnames, ('mhit1', 'mhitk')):
+                        if mn:
+                            out[rate][n] = \
+                                100.0 * sum(r[2][h] for r in res) / mn
         if self.logger and (self.dist_ctx is None or self.dist_ctx.is_main):
             info = {'info': ['Test Epoch: {}({:.0f}%)'.format(epoch, 100.)]}
             self.logger.append(info, 'test', mean=False)
             self.logger.write('test', [n + '@{}'.format(r) for r in out
-                                       for n in all_names])
+                                       for n in out[r]])
         return out
 
     # -------------------------------------------------------- fast GPU eval

@@ -97,6 +97,11 @@ std::vector<at::Tensor> lm_head_ce(at::Tensor x, at::Tensor packed,
                                    at::Tensor bias, at::Tensor labels,
                                    at::Tensor vocab_mask, int64_t V,
                                    int64_t E, int64_t splits);
+std::vector<at::Tensor> lm_head_topk(at::Tensor x, at::Tensor packed,
+                                     at::Tensor bias, at::Tensor labels,
+                                     at::Tensor vocab_mask, int64_t V,
+                                     int64_t E, int64_t k, int64_t splits);
+int64_t lm_head_topk_splits(int64_t M, int64_t V);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bn_relu_fwd", &bn_relu_fwd, "fused sBN+ReLU forward");
@@ -155,4 +160,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "one-time padded bf16 repack of the LM vocabulary head");
     m.def("lm_head_ce", &lm_head_ce,
           "fused vocabulary projection + cross-entropy (no logits written)");
+    m.def("lm_head_topk", &lm_head_topk,
+          "fused vocabulary projection + top-k + log-sum-exp (no logits "
+          "written)");
+    m.def("lm_head_topk_splits", &lm_head_topk_splits,
+          "lm_head_topk's own choice of splits for M rows");
 }

@@ -346,6 +346,70 @@ def lm_head_ce(x, packed, bias, labels, vocab_mask, V, E, splits=0):
     return lse - logits.gather(1, labels.long().view(-1, 1)).squeeze(1), lse
 
 
+LM_HEAD_MAX_K = 8   # capacity of lm_head_topk's per-lane lists
+
+
+def lm_head_topk(x, packed, bias, labels, vocab_mask, V, E, k, splits=0):
+    """Vocabulary projection fused with top-k: x (M, E), packed from
+    lm_head_pack, bias (V,) fp32 or None, labels (M,) int64 or None,
+    vocab_mask (V,) fp32 or None, 1 <= k <= min(8, V) -> (top_val (M, k)
+    fp32, top_idx (M, k) int64, row_lse (M,) fp32, row_nll (M,) fp32; empty
+    without labels).
+
+    The logits are lm_head_ce's (fp32, a vocab-masked column exactly 0 and
+    still a candidate, padded columns never returned).  Row i holds its k
+    largest logits in descending order, among equal logits the lower column
+    first; log-probabilities are top_val - row_lse[:, None].  On the GPU one
+    pass over the vocabulary keeps a running top-k next to the running
+    log-sum-exp (ops/csrc/lm_head_topk.hip); `splits` as in lm_head_ce, and
+    for a given value the four outputs are bit-reproducible.  On the CPU, and
+    under HETEROFL_FORCE_EAGER=1, fp32 logits and a stable descending sort:
+    the numerics oracle.
+
+    Measured on MI355X (profiles/lm_inferbench.txt, V = 33278, E in {256,
+    64, 16}, M in {640, 32768}): 1.11x - 1.30x of lm_head_ce's time at k = 1,
+    1.78x - 2.83x at k = 5, 2.45x - 4.63x at k = 8, and 0.05x - 0.61x of the
+    two-step bf16 F.linear + torch.topk + lm_ce_fwd at every point, which is
+    why there is no router next to lm_head_route for it."""
+    if not 1 <= k <= min(LM_HEAD_MAX_K, V):
+        raise ValueError('lm_head_topk: 1 <= k <= 8 and k <= V, got k={} '
+                         'for V={}'.format(k, V))
+    if use_native(x):
+        ext = require_native()
+        none = torch.Tensor()
+        val, idx, lse, nll = ext.lm_head_topk(
+            x.contiguous(), packed,
+            bias.float().contiguous() if bias is not None else none,
+            labels.long().contiguous() if labels is not None else none,
+            vocab_mask.float().contiguous() if vocab_mask is not None
+            else none, V, E, k, splits)
+        return val, idx, lse, nll
+    logits = x.float() @ packed[:V, :E].float().t()
+    if bias is not None:
+        logits = logits + bias.float()
+    if vocab_mask is not None:
+        logits = logits.masked_fill(vocab_mask.view(1, V) == 0, 0)
+    lse = torch.logsumexp(logits, dim=1)
+    nll = logits.new_empty(0)
+    if labels is not None:
+        nll = lse - logits.gather(1, labels.long().view(-1, 1)).squeeze(1)
+    # torch.sort(logits, descending=True, stable=True)[:, :k], with the
+    # columns under the row's k-th value dropped before the sort (they can
+    # not be returned, and sorting the whole vocabulary costs seconds per
+    # window set).  nonzero lists the rest by row, then ascending column;
+    # two stable sorts order them by row, then value descending, and keep
+    # the ascending columns among equal values.
+    kth = torch.topk(logits, k, dim=1).values[:, -1:]
+    keep = logits >= kth
+    row, col = keep.nonzero(as_tuple=True)
+    v = logits[row, col]
+    o = torch.sort(v, descending=True, stable=True).indices
+    o = o[torch.sort(row[o], stable=True).indices]
+    first = keep.sum(1).cumsum(0) - keep.sum(1)
+    pick = o[first.view(-1, 1) + torch.arange(k, device=x.device)]
+    return v[pick], col[pick], lse, nll
+
+
 def lm_head_route(M, E, V):
     """Router of NativeLMInference(head='auto'): True sends the head to
     lm_head_ce, False to the two-step bf16 F.linear + lm_ce_fwd.  The sweep

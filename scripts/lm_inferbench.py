@@ -12,7 +12,14 @@ M = 640.
 Part 2 — a whole synthetic WikiText2-shaped test set (HETEROFL_BENCH_TOKENS
 tokens in the train stream, an eighth of that in the test stream, the real
 vocabulary): FedRunner.test through the default eager loop, through
-HETEROFL_NATIVE_LM_EVAL=1, and FedRunner.test_lm_levels for a1-b1-c1-d1-e1.
+HETEROFL_NATIVE_LM_EVAL=1, and FedRunner.test_lm_levels for a1-b1-c1-d1-e1;
+the two native ones once more with HETEROFL_LM_TOPK=5.
+
+Part 3 (--topk) — the fill-mask head on the inputs of part 1, k in {1, 5,
+8}: lm_head_topk against lm_head_ce and against the two-step baseline bf16
+F.linear + torch.topk(logits.float(), k) + lm_ce_fwd, and a `splits` sweep at
+M = 640.  --append adds the run to the --out file as a new section instead
+of rewriting it.
 """
 import argparse
 import os
@@ -25,7 +32,8 @@ import torch
 import torch.nn.functional as F
 
 from heterofl_amd.ops import require_native
-from heterofl_amd.ops.fused import lm_head_ce, lm_head_pack, lm_head_route
+from heterofl_amd.ops.fused import (lm_head_ce, lm_head_pack, lm_head_route,
+                                    lm_head_topk)
 
 V = 33278
 
@@ -118,6 +126,47 @@ def bench_head(emit, dev):
         emit(f'{E:4d} ' + ' '.join(f'{t:8.1f}' for t in ts))
 
 
+def bench_topk(emit, dev):
+    ext = require_native()
+    none = torch.Tensor()
+    emit(f'-- fill-mask head, V={V}, bf16 x (us): lm_head_topk vs lm_head_ce '
+         f'vs bf16 F.linear + torch.topk(fp32) + lm_ce_fwd --')
+    emit(f'{"M":>6} {"E":>4} {"k":>2} {"topk":>9} {"ce":>9} {"gemm+topk":>10} '
+         f'{"topk/ce":>8} {"topk/gemm":>10} {"idx agree":>10}')
+    for E in (256, 64, 16):
+        for M in (640, 32768):
+            x, w, b, y = _head_inputs(M, E, dev)
+            packed = lm_head_pack(w, b)
+            w16, b16 = w.bfloat16(), b.bfloat16()
+            for k in (1, 5, 8):
+                def gemm():
+                    logits = F.linear(x, w16, b16)
+                    top = torch.topk(logits.float(), k)
+                    return top, ext.lm_ce_fwd(logits, y, none, 1)[1]
+
+                tt, tc, tg = time_alternating([
+                    lambda: lm_head_topk(x, packed, b, y, None, V, E, k),
+                    lambda: lm_head_ce(x, packed, b, y, None, V, E), gemm],
+                    iters=10 if M == 640 else 3)
+                # the share of rows on which the two routes name the same
+                # columns (the gemm one ranks bf16-rounded logits)
+                idx = lm_head_topk(x, packed, b, y, None, V, E, k)[1]
+                same = (idx == gemm()[0].indices).all(1).float().mean().item()
+                emit(f'{M:6d} {E:4d} {k:2d} {tt:9.1f} {tc:9.1f} {tg:10.1f} '
+                     f'{tt / tc:8.2f} {tt / tg:10.2f} {same:10.3f}')
+    emit('-- lm_head_topk, M=640, k=5: time (us) by splits (0 = host '
+         'choice) --')
+    sweep = (0, 1, 13, 26, 52, 104, 208)
+    emit(f'{"E":>4} ' + ' '.join(f'{s:>8d}' for s in sweep))
+    for E in (256, 64, 16):
+        x, w, b, y = _head_inputs(640, E, dev)
+        packed = lm_head_pack(w, b)
+        ts = time_alternating([
+            (lambda s=s: lm_head_topk(x, packed, b, y, None, V, E, 5,
+                                      splits=s)) for s in sweep])
+        emit(f'{E:4d} ' + ' '.join(f'{t:8.1f}' for t in ts))
+
+
 def _wall(fn, reps=3):
     fn()
     torch.cuda.synchronize()
@@ -184,6 +233,21 @@ def bench_runner(emit, dev):
              f'(different masks, mask_rate {cfg["mask_rate"]})')
     t_levels = _wall(lambda: runner.test_lm_levels(1), 2)
     emit(f'{"test_lm_levels a1-b1-c1-d1-e1 (5 levels)":44} {t_levels:9.1f}')
+    # the same two native evaluations with token accuracy from the same pass
+    os.environ['HETEROFL_LM_TOPK'] = '5'
+    os.environ['HETEROFL_NATIVE_LM_EVAL'] = '1'
+    t_native5 = _wall(test, 3)
+    native5 = dict(runner.logger.mean)
+    os.environ.pop('HETEROFL_NATIVE_LM_EVAL', None)
+    t_levels5 = _wall(lambda: runner.test_lm_levels(1), 2)
+    os.environ.pop('HETEROFL_LM_TOPK', None)
+    emit(f'{"test(), native, HETEROFL_LM_TOPK=5":44} {t_native5:9.1f}')
+    emit(f'{"  ratio knob on/off":44} {t_native5 / t_native:9.3f}')
+    emit(f'{"test_lm_levels, HETEROFL_LM_TOPK=5":44} {t_levels5:9.1f}')
+    emit(f'{"  ratio knob on/off":44} {t_levels5 / t_levels:9.3f}')
+    for k in sorted(native5):
+        if 'Accuracy' in k:
+            emit(f'  {k}: {native5[k]:.4f}')
 
 
 def main():
@@ -191,6 +255,10 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--skip-head', action='store_true')
     ap.add_argument('--skip-runner', action='store_true')
+    ap.add_argument('--topk', action='store_true',
+                    help='run part 3 (the fill-mask head)')
+    ap.add_argument('--append', action='store_true',
+                    help='add to the --out file instead of rewriting it')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('lm_inferbench needs a GPU')
@@ -204,11 +272,13 @@ def main():
     emit(f'device: {torch.cuda.get_device_name(0)}')
     if not args.skip_head:
         bench_head(emit, dev)
+    if args.topk:
+        bench_topk(emit, dev)
     if not args.skip_runner:
         bench_runner(emit, dev)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
+        with open(args.out, 'a' if args.append else 'w') as f:
             f.write('\n'.join(lines) + '\n')
 
 
