@@ -26,6 +26,18 @@
 // tests/test_gpu.py::test_mfma_probe_layout): A: lane l holds
 // A[row=l%16][k=(l/16)*8+j]; B: B[k=(l/16)*8+j][col=l%16]; C/D:
 // row=(l/16)*4+reg, col=l%16.
+//
+// Kernel families, fastest route first (host layer at the bottom routes):
+//   resident  conv_{fwd,bwd_data,bwd_weight}_resident_kernel: window staged
+//             once per block (per sample segment for bwd-weight) as raw T,
+//             offset tables instead of k-loop div/mod, double-buffered
+//             tiles, one barrier per k-step.  Taken wherever the staged
+//             geometry holds and the slice fits 64 KB of LDS;
+//             HETEROFL_CONV_RESIDENT=0 turns it off.
+//   staged    conv_*_staged_kernel: window restaged per k-step; the
+//             fallback and the bit-exact oracle of the resident kernels.
+//   gather    conv_fwd_kernel, conv_bwd_data{,_s2}_kernel,
+//             conv_bwd_weight_kernel: any geometry, fp8 instantiations.
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -1446,9 +1458,568 @@ conv_bwd_weight_staged_kernel(const T* __restrict__ dy,
             }
 }
 
+// ------------------------------------------------ resident-window kernels
+// The staged kernels above restage their window on every k-step and pay
+// runtime div/mod per staged element; they are bound by VALU issue, not by
+// memory (profiles/NOTES.md, "resident window").  The resident variants
+// stage the window ONCE per block for the block's whole K/J slice, as raw T
+// (no float round trip), and turn every k -> (channel, kh, kw) decode into
+// a per-block offset table built in the prologue, so the k-loop carries no
+// integer division: a B element is one LDS read at table[k] + pixel_base.
+// Operands, their order and the BK chunking are those of the staged
+// kernels, so results are bit-identical (HETEROFL_CONV_RESIDENT=0 routes
+// back to them for A/B).
+//
+// Window layout: rows of `width` elements, each preceded by a WGAP-element
+// zero gap; the gap serves as the row's left pad and as the right pad of
+// the row before it (pad <= WGAP/2), and one trailing gap closes the last
+// row.  Row stride S = width + WGAP keeps rows 16-byte aligned whenever
+// `width` allows 16-byte global loads.
+constexpr int WGAP = 8;
+
+template <typename T> struct RawOf { typedef float type; };
+template <> struct RawOf<__hip_bfloat16> { typedef unsigned short type; };
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+
+__device__ __forceinline__ void st8_raw(unsigned short* dst,
+                                        const unsigned short* v) {
+    u32x4 t;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        t[j] = (unsigned)v[2 * j] | ((unsigned)v[2 * j + 1] << 16);
+    *(u32x4*)dst = t;
+}
+__device__ __forceinline__ void st8_raw(float* dst, const float* v) {
+    st8_lds(dst, v);
+}
+
+// Stage nch channels x nrows rows of a dense image (row length `width`,
+// channel stride chs) into `win`; window row rr is image row row0 + rr,
+// zero-filled outside [0, img_rows).  `vec`: 16-byte loads are legal.
+template <typename R>
+__device__ __forceinline__ void stage_window(R* win, const R* src, long chs,
+                                             int nch, int nrows, int row0,
+                                             int img_rows, int width, int S,
+                                             bool vec, int tid) {
+    constexpr int VE = 16 / (int)sizeof(R);
+    const int nrt = nch * nrows;
+    if (vec) {
+        const int vpr = width / VE;
+        const int nvec = nrt * vpr;
+#pragma unroll 4
+        for (int v = tid; v < nvec; v += 256) {
+            const int rowi = v / vpr, wv = v - rowi * vpr;
+            const int cc = rowi / nrows, rr = rowi - cc * nrows;
+            const int ir = row0 + rr;
+            u32x4 val = {0u, 0u, 0u, 0u};
+            if (ir >= 0 && ir < img_rows)
+                val = *(const u32x4*)(src + (long)cc * chs + ir * width
+                                      + wv * VE);
+            *(u32x4*)(win + rowi * S + WGAP + wv * VE) = val;
+        }
+    } else {
+        const int ntot = nrt * width;
+        for (int e = tid; e < ntot; e += 256) {
+            const int rowi = e / width, ww = e - rowi * width;
+            const int cc = rowi / nrows, rr = rowi - cc * nrows;
+            const int ir = row0 + rr;
+            R val = (R)0;
+            if (ir >= 0 && ir < img_rows)
+                val = src[(long)cc * chs + ir * width + ww];
+            win[rowi * S + WGAP + ww] = val;
+        }
+    }
+    for (int i = tid; i < (nrt + 1) * WGAP; i += 256)
+        win[(i >> 3) * S + (i & (WGAP - 1))] = (R)0;
+}
+
+// flags: bit 0 = window rows take 16-byte loads, bit 1 = weight rows take
+// float4 loads (K % 4 == 0, base aligned).  Dynamic LDS: the window, then
+// the ushort k-offset table at byte offset tab_bytes (nkc*BK entries).
+// Requires P % BP == 0 (the staged route's whole-row tiles).
+template <typename T>
+__global__ void __launch_bounds__(256)
+conv_fwd_resident_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                         const float* __restrict__ bias,
+                         const T* __restrict__ residual, T* __restrict__ y,
+                         float* __restrict__ partial, ConvGeom gm, int splitk,
+                         int tab_bytes, int flags) {
+    typedef typename RawOf<T>::type R;
+    extern __shared__ __align__(16) unsigned char dyn_lds[];
+    __shared__ T a_lds[2][BM][LDK];
+    __shared__ T b_lds[2][BP][LDK];
+    R* win = (R*)dyn_lds;
+    unsigned short* koff = (unsigned short*)(dyn_lds + tab_bytes);
+    const int g = blockIdx.z % gm.G;
+    const int sp = blockIdx.z / gm.G;
+    const int m0 = blockIdx.x * BM;
+    const int p0 = blockIdx.y * BP;
+    const int kk2 = gm.khw * gm.khw;
+    const int K = gm.Cin * kk2;
+    const int M = gm.Cout;
+    const int OHW = gm.OH * gm.OW;
+    const int HW = gm.H * gm.W;
+    const int tid = threadIdx.x;
+    const int l = tid & (WAVE - 1);
+    const int wave = tid / WAVE;
+    const int wm = (wave >> 1) * 32;
+    const int wp = (wave & 1) * 32;
+    const int nkc = ((K + BK - 1) / BK + splitk - 1) / splitk;
+    const int ks = sp * nkc * BK;
+    const int ke = min(K, ks + nkc * BK);
+    // tile geometry: one sample, whole output rows
+    const int n = p0 / OHW;
+    const int oh0 = (p0 - n * OHW) / gm.OW;
+    const int nrow_out = BP / gm.OW;
+    const int rows_in = (nrow_out - 1) * gm.stride + gm.khw;
+    const int ih0 = oh0 * gm.stride - gm.pad;   // window top (may be < 0)
+    const long xn = ((long)n * gm.G * gm.Cin + (long)g * gm.Cin) * HW;
+    const int S = gm.W + WGAP;
+    const int mm_a = tid >> 2, kkb = (tid & 3) * 8;
+    const int pp_b = tid >> 2;
+
+    // prologue: window for the slice's whole channel span + k-offset table
+    const int cin_lo = ks / kk2;
+    if (ks < ke) {   // empty split slices stage nothing and write zeros
+        const int nch = (ke - 1) / kk2 - cin_lo + 1;
+        stage_window<R>(win, (const R*)x + xn + (long)cin_lo * HW, HW, nch,
+                        rows_in, ih0, gm.H, gm.W, S, flags & 1, tid);
+        for (int i = tid; i < nkc * BK; i += 256) {
+            const int k = ks + i;
+            int off = 0;
+            if (k < ke) {
+                const int cin = k / kk2, r = k - cin * kk2;
+                const int kh = r / gm.khw, kw = r - kh * gm.khw;
+                off = ((cin - cin_lo) * rows_in + kh) * S + kw;
+            }
+            koff[i] = (unsigned short)off;
+        }
+    }
+    __syncthreads();
+    const int pbase = (pp_b / gm.OW) * gm.stride * S + WGAP
+                      + (pp_b % gm.OW) * gm.stride - gm.pad;
+    const bool m_full = (m0 + BM <= M);
+    const float* wrow0 = w + (long)(g * gm.Cout + m0 + mm_a) * K + kkb;
+
+    f32x4 acc[2][2] = {};
+    float va[8];
+    auto load_a = [&](int k0) {
+        const float* wrow = wrow0 + k0;
+        if ((flags & 2) && m_full && k0 + BK <= ke) {   // block-uniform
+            const f32x4 lo = *(const f32x4*)wrow;
+            const f32x4 hi = *(const f32x4*)(wrow + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                va[j] = lo[j];
+                va[4 + j] = hi[j];
+            }
+        } else {
+            const bool mok = (m0 + mm_a < M);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                va[j] = (mok && k0 + kkb + j < ke) ? wrow[j] : 0.f;
+        }
+    };
+    auto build_b = [&](int k0, T* dst) {
+        const u32x4 kv = *(const u32x4*)(koff + (k0 - ks) + kkb);
+        R vb[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int off = (kv[j >> 1] >> ((j & 1) * 16)) & 0xffff;
+            vb[j] = win[pbase + off];
+        }
+        if (k0 + BK > ke) {   // ragged last chunk (ke == K here)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (k0 + kkb + j >= ke) vb[j] = (R)0;
+        }
+        st8_raw((R*)dst, vb);
+    };
+    // double-buffered k-loop: one barrier per k-step
+    if (ks < ke) {
+        load_a(ks);
+        st8_lds(&a_lds[0][mm_a][kkb], va);
+        build_b(ks, &b_lds[0][pp_b][kkb]);
+        if (ks + BK < ke) load_a(ks + BK);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int k0 = ks; k0 < ke; k0 += BK) {
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+            for (int fp = 0; fp < 2; ++fp)
+                acc[fm][fp] = mfma_tile<T>(
+                    &a_lds[cur][wm + fm * 16 + (l & 15)][0],
+                    &b_lds[cur][wp + fp * 16 + (l & 15)][0], acc[fm][fp]);
+        if (k0 + BK < ke) {
+            st8_lds(&a_lds[cur ^ 1][mm_a][kkb], va);
+            build_b(k0 + BK, &b_lds[cur ^ 1][pp_b][kkb]);
+            if (k0 + 2 * BK < ke) load_a(k0 + 2 * BK);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const long slab = (long)sp * gm.N * gm.G * gm.Cout * OHW;
+    const long yb0 = ((long)n * gm.G * gm.Cout + (long)g * gm.Cout) * OHW
+                     + (p0 - n * OHW);
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fp = 0; fp < 2; ++fp) {
+            const int pp = wp + fp * 16 + (l & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
+                if (m < M) {
+                    const long off = yb0 + pp + (long)m * OHW;
+                    float v = acc[fm][fp][r];
+                    if (splitk == 1) {
+                        if (bias) v += bias[g * gm.Cout + m];
+                        if (residual) v += ld_f32(residual + off);
+                        st_f32(y + off, v);
+                    } else {
+                        partial[slab + off] = v;
+                    }
+                }
+            }
+        }
+}
+
+// Stride-1 bwd-data mirror: the dy window of the block's whole J slice is
+// resident; joff[j] holds the window offset of (cout, kh, kw) with the
+// (khw-1-kh, khw-1-kw) flip folded in (so offsets stay non-negative), and
+// woff[j] the strided weight offset cout*K + tap.  Dynamic LDS: window,
+// int woff table at woff_bytes, ushort joff table at joff_bytes.
+template <typename T>
+__global__ void __launch_bounds__(256)
+conv_bwd_data_resident_kernel(const T* __restrict__ dy,
+                              const float* __restrict__ w,
+                              T* __restrict__ dx, float* __restrict__ partial,
+                              ConvGeom gm, int splitk, int woff_bytes,
+                              int joff_bytes, int flags) {
+    typedef typename RawOf<T>::type R;
+    extern __shared__ __align__(16) unsigned char dyn_lds[];
+    __shared__ T a_lds[2][BM][LDK];
+    __shared__ T b_lds[2][BP][LDK];
+    R* win = (R*)dyn_lds;
+    int* woff = (int*)(dyn_lds + woff_bytes);
+    unsigned short* joff = (unsigned short*)(dyn_lds + joff_bytes);
+    const int g = blockIdx.z % gm.G;
+    const int sp = blockIdx.z / gm.G;
+    const int c0 = blockIdx.x * BM;
+    const int q0 = blockIdx.y * BP;
+    const int kk2 = gm.khw * gm.khw;
+    const int J = gm.Cout * kk2;
+    const int K = gm.Cin * kk2;
+    const int HW = gm.H * gm.W;
+    const int OHW = gm.OH * gm.OW;
+    const int tid = threadIdx.x;
+    const int l = tid & (WAVE - 1);
+    const int wave = tid / WAVE;
+    const int wm = (wave >> 1) * 32;
+    const int wp = (wave & 1) * 32;
+    const int njc = ((J + BK - 1) / BK + splitk - 1) / splitk;
+    const int js = sp * njc * BK;
+    const int je = min(J, js + njc * BK);
+    // tile geometry (stride 1)
+    const int n = q0 / HW;
+    const int ih0 = (q0 - n * HW) / gm.W;
+    const int nrow_in = BP / gm.W;
+    const int rows_w = nrow_in + gm.khw - 1;
+    const int ohs_min = ih0 + gm.pad - (gm.khw - 1);
+    const long dyn = ((long)n * gm.G * gm.Cout + (long)g * gm.Cout) * OHW;
+    const int S = gm.OW + WGAP;
+    const int cc_a = tid >> 2, jjb = (tid & 3) * 8;
+
+    const int co_lo = js / kk2;
+    if (js < je) {
+        const int nch = (je - 1) / kk2 - co_lo + 1;
+        stage_window<R>(win, (const R*)dy + dyn + (long)co_lo * OHW, OHW, nch,
+                        rows_w, ohs_min, gm.OH, gm.OW, S, flags & 1, tid);
+        for (int i = tid; i < njc * BK; i += 256) {
+            const int j = js + i;
+            int off = 0, wo = 0;
+            if (j < je) {
+                const int cout = j / kk2, r = j - cout * kk2;
+                const int kh = r / gm.khw, kw = r - kh * gm.khw;
+                off = ((cout - co_lo) * rows_w + (gm.khw - 1 - kh)) * S
+                      + (gm.khw - 1 - kw);
+                wo = cout * K + r;
+            }
+            joff[i] = (unsigned short)off;
+            woff[i] = wo;
+        }
+    }
+    __syncthreads();
+    // needed dy[ohs = ih + pad - kh][ows = iw + pad - kw]; window row
+    // ohs - ohs_min = ihl + (khw-1-kh), column WGAP + ows
+    const int pbase = (cc_a / gm.W) * S + WGAP + (cc_a % gm.W) + gm.pad
+                      - (gm.khw - 1);
+    const bool c_ok = (c0 + cc_a < gm.Cin);
+    const float* wbase = w + (long)g * gm.Cout * K + (long)(c0 + cc_a) * kk2;
+
+    f32x4 acc[2][2] = {};
+    float va[8];
+    auto load_a = [&](int j0) {
+        const int* wo = woff + (j0 - js) + jjb;
+        const u32x4 lo = *(const u32x4*)wo;
+        const u32x4 hi = *(const u32x4*)(wo + 4);
+        if (j0 + BK <= je) {   // block-uniform interior chunk
+#pragma unroll
+            for (int j8 = 0; j8 < 4; ++j8) {
+                va[j8] = c_ok ? wbase[lo[j8]] : 0.f;
+                va[4 + j8] = c_ok ? wbase[hi[j8]] : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int j8 = 0; j8 < 4; ++j8) {
+                va[j8] = (c_ok && j0 + jjb + j8 < je) ? wbase[lo[j8]] : 0.f;
+                va[4 + j8] = (c_ok && j0 + jjb + 4 + j8 < je) ? wbase[hi[j8]]
+                                                              : 0.f;
+            }
+        }
+    };
+    auto build_b = [&](int j0, T* dst) {
+        const u32x4 jv = *(const u32x4*)(joff + (j0 - js) + jjb);
+        R vb[8];
+#pragma unroll
+        for (int j8 = 0; j8 < 8; ++j8) {
+            const int off = (jv[j8 >> 1] >> ((j8 & 1) * 16)) & 0xffff;
+            vb[j8] = win[pbase + off];
+        }
+        if (j0 + BK > je) {
+#pragma unroll
+            for (int j8 = 0; j8 < 8; ++j8)
+                if (j0 + jjb + j8 >= je) vb[j8] = (R)0;
+        }
+        st8_raw((R*)dst, vb);
+    };
+    if (js < je) {
+        load_a(js);
+        st8_lds(&a_lds[0][cc_a][jjb], va);
+        build_b(js, &b_lds[0][cc_a][jjb]);
+        if (js + BK < je) load_a(js + BK);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int j0 = js; j0 < je; j0 += BK) {
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+            for (int fp = 0; fp < 2; ++fp)
+                acc[fm][fp] = mfma_tile<T>(
+                    &a_lds[cur][wm + fm * 16 + (l & 15)][0],
+                    &b_lds[cur][wp + fp * 16 + (l & 15)][0], acc[fm][fp]);
+        if (j0 + BK < je) {
+            st8_lds(&a_lds[cur ^ 1][cc_a][jjb], va);
+            build_b(j0 + BK, &b_lds[cur ^ 1][cc_a][jjb]);
+            if (j0 + 2 * BK < je) load_a(j0 + 2 * BK);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const long slab = (long)sp * gm.N * gm.G * gm.Cin * HW;
+    const long xb0 = ((long)n * gm.G * gm.Cin + (long)g * gm.Cin) * HW
+                     + (q0 - n * HW);
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fp = 0; fp < 2; ++fp) {
+            const int qq = wp + fp * 16 + (l & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = c0 + wm + fm * 16 + (l >> 4) * 4 + r;
+                if (c < gm.Cin) {
+                    const long off = xb0 + qq + (long)c * HW;
+                    if (splitk == 1)
+                        st_f32(dx + off, acc[fm][fp][r]);
+                    else
+                        partial[slab + off] = acc[fm][fp][r];
+                }
+            }
+        }
+}
+
+// 8 consecutive raw elements held packed (one 16-byte register quad per 8
+// bf16, two per 8 fp32)
+template <typename R> struct Pack8 { u32x4 v[sizeof(R) / 2]; };
+
+template <typename R>
+__device__ __forceinline__ Pack8<R> ld8_pack(const R* p, bool vec) {
+    Pack8<R> r;
+    if (vec) {
+#pragma unroll
+        for (int i = 0; i < (int)sizeof(R) / 2; ++i)
+            r.v[i] = ((const u32x4*)p)[i];
+    } else if constexpr (sizeof(R) == 2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            r.v[0][j] = (unsigned)p[2 * j] | ((unsigned)p[2 * j + 1] << 16);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            r.v[j >> 2][j & 3] = __float_as_uint(p[j]);
+    }
+    return r;
+}
+template <typename R>
+__device__ __forceinline__ void st8_pack(R* dst, const Pack8<R>& r) {
+#pragma unroll
+    for (int i = 0; i < (int)sizeof(R) / 2; ++i) ((u32x4*)dst)[i] = r.v[i];
+}
+
+// bwd-weight: the channel span is fixed per block and every p-step covers
+// whole output rows of one sample, so the x window is staged once per
+// SAMPLE SEGMENT of the block's p-chunk (not once per 32-pixel step) and a
+// p-step only moves the window row base.  The p-loop carries no division:
+// (n, hw, oh) advance as counters, each thread's 8 pixel offsets are
+// prologue constants, and the dy tile is one packed 16-byte-per-8-pixels
+// copy (all 32 pixels of a step are live: chunks and P are BK-aligned).
+// flags: bit 0 = x rows take 16-byte loads, bit 1 = dy takes them.
+template <typename T>
+__global__ void __launch_bounds__(256)
+conv_bwd_weight_resident_kernel(const T* __restrict__ dy,
+                                const T* __restrict__ x,
+                                float* __restrict__ out, ConvGeom gm,
+                                int splitp, int flags) {
+    typedef typename RawOf<T>::type R;
+    extern __shared__ __align__(16) unsigned char dyn_lds[];
+    __shared__ T a_lds[2][BM][LDK];
+    __shared__ T b_lds[2][BP][LDK];
+    R* win = (R*)dyn_lds;
+    const int g = blockIdx.z % gm.G;
+    const int sp = blockIdx.z / gm.G;
+    const int m0 = blockIdx.x * BM;
+    const int k0 = blockIdx.y * BP;
+    const int kk2 = gm.khw * gm.khw;
+    const int K = gm.Cin * kk2;
+    const int M = gm.Cout;
+    const int OHW = gm.OH * gm.OW;
+    const int P = gm.N * OHW;
+    const int HW = gm.H * gm.W;
+    const int tid = threadIdx.x;
+    const int l = tid & (WAVE - 1);
+    const int wave = tid / WAVE;
+    const int wm = (wave >> 1) * 32;
+    const int wp = (wave & 1) * 32;
+    const int pchunk0 = (P + splitp - 1) / splitp;
+    const int pchunk = ((pchunk0 + BK - 1) / BK) * BK;  // BK-aligned chunks
+    const int pstart = sp * pchunk;
+    const int pend = min(P, pstart + pchunk);
+    const int cin0 = k0 / kk2;
+    const int nch = min(gm.Cin - 1, (k0 + BP - 1) / kk2) - cin0 + 1;
+    const int nrow_out = BK / gm.OW;          // output rows per p-step
+    const int S = gm.W + WGAP;
+    const int step_rows = nrow_out * gm.stride * S;
+    // per-thread B ownership: fixed k, 8 consecutive pixels
+    const int kk_b = (tid >> 2) & 63, ppb = (tid & 3) * 8;
+    const int k_b = k0 + kk_b;
+    const bool k_ok = (k_b < K);
+    int cin_b = cin0, kh_b = 0, kw_b = 0;
+    if (k_ok) {
+        cin_b = k_b / kk2;
+        const int r = k_b - cin_b * kk2;
+        kh_b = r / gm.khw;
+        kw_b = r - kh_b * gm.khw;
+    }
+    int poff[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int pp = ppb + j;
+        poff[j] = (pp / gm.OW) * gm.stride * S + (pp % gm.OW) * gm.stride;
+    }
+    // per-thread A ownership: one dy row, the same 8 pixels
+    const int mm_a = tid >> 2;
+    const bool m_ok = (m0 + mm_a < M);
+    const long dy_ns = (long)gm.G * gm.Cout * OHW;
+    const R* dyrow = (const R*)dy + ((long)g * gm.Cout + m0 + mm_a) * OHW
+                     + ppb;
+    const bool dvec = (flags & 2) != 0;
+    auto load_a = [&](int n_, int hw_) {
+        Pack8<R> r = {};
+        if (m_ok) r = ld8_pack<R>(dyrow + (long)n_ * dy_ns + hw_, dvec);
+        return r;
+    };
+    auto build_b = [&](int base, T* dst) {
+        R vb[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            vb[j] = k_ok ? win[base + poff[j]] : (R)0;
+        st8_raw((R*)dst, vb);
+    };
+
+    f32x4 acc[2][2] = {};
+    // chunk position, advanced by counters from here on
+    int n = pstart / OHW;
+    int hw = pstart - n * OHW;
+    int oh = hw / gm.OW;
+    int cur = 0;
+    for (int p0 = pstart; p0 < pend;) {
+        // one sample segment of the chunk: nst p-steps, one window
+        const int seg_px = min(pend - p0, OHW - hw);
+        const int nst = seg_px / BK;
+        const int nrows = (nst * nrow_out - 1) * gm.stride + gm.khw;
+        const long xn = ((long)n * gm.G * gm.Cin + (long)g * gm.Cin + cin0)
+                        * HW;
+        stage_window<R>(win, (const R*)x + xn, HW, nch, nrows,
+                        oh * gm.stride - gm.pad, gm.H, gm.W, S, flags & 1,
+                        tid);
+        __syncthreads();
+        const int kbase = ((cin_b - cin0) * nrows + kh_b) * S + WGAP + kw_b
+                          - gm.pad;
+        Pack8<R> ra = load_a(n, hw);
+        st8_pack((R*)&a_lds[cur][mm_a][ppb], ra);
+        build_b(kbase, &b_lds[cur][kk_b][ppb]);
+        if (nst > 1) ra = load_a(n, hw + BK);
+        __syncthreads();
+        for (int t = 0; t < nst; ++t) {
+#pragma unroll
+            for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+                for (int fp = 0; fp < 2; ++fp)
+                    acc[fm][fp] = mfma_tile<T>(
+                        &a_lds[cur][wm + fm * 16 + (l & 15)][0],
+                        &b_lds[cur][wp + fp * 16 + (l & 15)][0],
+                        acc[fm][fp]);
+            if (t + 1 < nst) {
+                st8_pack((R*)&a_lds[cur ^ 1][mm_a][ppb], ra);
+                build_b(kbase + (t + 1) * step_rows,
+                        &b_lds[cur ^ 1][kk_b][ppb]);
+                if (t + 2 < nst) ra = load_a(n, hw + (t + 2) * BK);
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        p0 += seg_px;
+        hw += seg_px;
+        oh += nst * nrow_out;
+        if (hw == OHW) {
+            hw = 0;
+            oh = 0;
+            ++n;
+        }
+    }
+    const long GK = (long)gm.G * gm.Cout * K;
+    float* slab = out + (long)sp * GK;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fp = 0; fp < 2; ++fp)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
+                const int k = k0 + wp + fp * 16 + (l & 15);
+                if (m < M && k < K)
+                    slab[(long)(g * gm.Cout + m) * K + k] = acc[fm][fp][r];
+            }
+}
+
 // ------------------------------------------------------------ host layer
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 
 // target concurrent-block count for the split-K/split-P decompositions
@@ -1459,6 +2030,44 @@ static int split_target() {
         return e ? std::atoi(e) : 1024;
     }();
     return t;
+}
+
+// resident-window routing.  HETEROFL_CONV_RESIDENT=0 (read on every call,
+// so one process can flip it) routes back to the staged kernels.  A slice
+// is resident only while static + dynamic LDS stays under the cap.  The
+// cap is 64 KB, the most a launch gets without a function attribute:
+// measured (profiles/convbench_resident.txt, shapes X96/X128), slices
+// between 53 KB (3 blocks/CU of 160 KB) and 64 KB (2 blocks/CU) still run
+// 2.4-2.7x faster resident than staged, so the lower-occupancy resident
+// kernel beats the fallback (HETEROFL_CONV_RESIDENT_LDS lowers the cap
+// for sweeps).
+static bool resident_on() {
+    const char* e = std::getenv("HETEROFL_CONV_RESIDENT");
+    return !(e && e[0] == '0');
+}
+static int resident_lds_cap() {
+    static int c = [] {
+        const char* e = std::getenv("HETEROFL_CONV_RESIDENT_LDS");
+        const int v = e ? std::atoi(e) : 65536;
+        return v > 65536 ? 65536 : v;
+    }();
+    return c;
+}
+static bool aligned16(const void* p) {
+    return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+// LDS plan of one resident launch (bytes); chunks = BK-chunks per slice,
+// tap2 = khw*khw, nchan = channels of the staged tensor, width = its row
+static bool resident_plan(int chunks, int tap2, int nchan, int rows,
+                          int width, int esz, int tab_entry_bytes,
+                          int* win_bytes) {
+    const int nch_max = std::min(nchan, (chunks * BK - 1) / tap2 + 2);
+    const long welems = (long)nch_max * rows * (width + WGAP) + WGAP;
+    if (welems >= 65536) return false;   // ushort offsets
+    *win_bytes = (int)((welems * esz + 15) / 16 * 16);
+    const int stat = 2 * (BM + BP) * LDK * esz;
+    return stat + *win_bytes + chunks * BK * tab_entry_bytes
+           <= resident_lds_cap();
 }
 
 #define DISPATCH_CONV_FT(t, ...)                                              \
@@ -1528,8 +2137,35 @@ at::Tensor conv_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
                                  <= MS_ROWS
                           && (BK / (gm.khw * gm.khw) + 2) <= WIN_CH
                           && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
+    // resident window: wherever the staged kernel is routed and the slice's
+    // window fits under the LDS cap
+    const int esz = (int)x.element_size();
+    const int nkc = (kchunks + splitk - 1) / splitk;
+    int win_bytes = 0;
+    const bool resident =
+        staged && !fp8 && resident_on() && P % BP == 0 && 2 * gm.pad <= WGAP
+        && resident_plan(nkc, gm.khw * gm.khw, gm.Cin,
+                         (BP / gm.OW - 1) * gm.stride + gm.khw, gm.W, esz, 2,
+                         &win_bytes);
     DISPATCH_CONV_FT(x.scalar_type(), {
-        if (staged_ms && !fp8) {
+        if (resident) {
+            const int flags =
+                ((gm.W % (16 / esz) == 0 && aligned16(x.data_ptr())) ? 1 : 0)
+                | ((K % 4 == 0 && aligned16(w.data_ptr())) ? 2 : 0);
+            hipLaunchKernelGGL((conv_fwd_resident_kernel<scalar_t>), grid,
+                               dim3(256), win_bytes + nkc * BK * 2, stream,
+                               (const scalar_t*)x.data_ptr(),
+                               w.data_ptr<float>(),
+                               bias.defined() ? bias.data_ptr<float>()
+                                              : nullptr,
+                               residual.defined()
+                                   ? (const scalar_t*)residual.data_ptr()
+                                   : nullptr,
+                               (scalar_t*)y.data_ptr(),
+                               splitk > 1 ? partial.data_ptr<float>()
+                                          : nullptr,
+                               gm, splitk, win_bytes, flags);
+        } else if (staged_ms && !fp8) {
             hipLaunchKernelGGL((conv_fwd_staged_ms_kernel<scalar_t, scalar_t,
                                                           scalar_t>),
                                grid, dim3(256), 0, stream,
@@ -1664,9 +2300,30 @@ at::Tensor conv_bwd_data(at::Tensor dy, at::Tensor w, int64_t groups,
                         && (BP / HWd) * (gm.H + gm.khw - 1) <= MS_ROWS
                         && (BK / (gm.khw * gm.khw) + 2) <= WIN_CH
                         && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
+    // resident dy window (2*pad >= khw-1: the geometry the staged kernel's
+    // own window addressing covers)
+    const int esz = (int)dy.element_size();
+    const int njc = (jchunks + splitk - 1) / splitk;
+    int win_bytes = 0;
+    const bool resident =
+        stg && !fp8 && resident_on() && 2 * gm.pad <= WGAP
+        && 2 * gm.pad >= gm.khw - 1
+        && resident_plan(njc, gm.khw * gm.khw, gm.Cout,
+                         BP / gm.W + gm.khw - 1, gm.OW, esz, 6, &win_bytes);
     DISPATCH_CONV_FT(dy.scalar_type(), {
         const bool q = fp8 && dy.scalar_type() == at::kBFloat16;
-        if (stg_ms && !q) {
+        if (resident) {
+            const int flags =
+                (gm.OW % (16 / esz) == 0 && aligned16(dyc.data_ptr())) ? 1 : 0;
+            hipLaunchKernelGGL((conv_bwd_data_resident_kernel<scalar_t>),
+                               grid, dim3(256), win_bytes + njc * BK * 6,
+                               stream, (const scalar_t*)dyc.data_ptr(),
+                               w.data_ptr<float>(), (scalar_t*)dx.data_ptr(),
+                               splitk > 1 ? partial.data_ptr<float>()
+                                          : nullptr,
+                               gm, splitk, win_bytes,
+                               win_bytes + njc * BK * 4, flags);
+        } else if (stg_ms && !q) {
             hipLaunchKernelGGL((conv_bwd_data_staged_ms_kernel<scalar_t,
                                                                scalar_t,
                                                                scalar_t>),
@@ -1795,6 +2452,41 @@ at::Tensor conv_bwd_weight(at::Tensor dy, at::Tensor x, int64_t groups,
                      && (gm.W + 2 * gm.pad) <= WIN_W - 2
                      && ((BK / gm.OW - 1) * gm.stride + gm.khw) <= WIN_ROWS
                      && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
+    // resident x window: one sample segment of the p-chunk at a time
+    const int esz = (int)x.element_size();
+    const int OHWw = gm.OH * gm.OW;
+    const int pchunk = (((P + splitp - 1) / splitp + BK - 1) / BK) * BK;
+    const long wwin = (long)std::min(gm.Cin, WWIN_CH)
+                          * ((std::min(pchunk, OHWw) / gm.OW - 1) * gm.stride
+                             + gm.khw) * (gm.W + WGAP) + WGAP;
+    const int wwin_bytes = (int)((wwin * esz + 15) / 16 * 16);
+    const bool resident = stg && !q && resident_on() && 2 * gm.pad <= WGAP
+                          && 2L * (BM + BP) * LDK * esz + wwin * esz
+                                 <= resident_lds_cap();
+    if (resident) {
+        const int flags =
+            ((gm.W % (16 / esz) == 0 && aligned16(x.data_ptr())) ? 1 : 0)
+            | (aligned16(dyc.data_ptr()) ? 2 : 0);
+        at::Tensor partials;
+        if (splitp > 1)
+            partials = at::empty({splitp, GK}, x.options().dtype(at::kFloat));
+        DISPATCH_CONV_FT(x.scalar_type(), {
+            hipLaunchKernelGGL((conv_bwd_weight_resident_kernel<scalar_t>),
+                               grid, dim3(256), wwin_bytes, stream,
+                               (const scalar_t*)dyc.data_ptr(),
+                               (const scalar_t*)x.data_ptr(),
+                               splitp > 1 ? partials.data_ptr<float>()
+                                          : dw.data_ptr<float>(),
+                               gm, (int)splitp, flags);
+        });
+        if (splitp > 1) {
+            const int blocks = (int)((GK + 255) / 256);
+            hipLaunchKernelGGL(splitp_reduce_kernel, dim3(blocks), dim3(256),
+                               0, stream, partials.data_ptr<float>(),
+                               dw.data_ptr<float>(), GK, splitp);
+        }
+        return dw;
+    }
     if (splitp == 1) {
         DISPATCH_CONV_FT(x.scalar_type(), {
             if (q)

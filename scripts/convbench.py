@@ -1,8 +1,14 @@
 #!/usr/bin/env python
-"""Per-shape A/B of the MFMA grouped conv vs MIOpen (F.conv2d): fwd,
-bwd-data, bwd-weight timed separately with hip events.  Run on a GPU box:
-    python scripts/convbench.py [iters]
+"""Per-shape A/B of the MFMA grouped conv: fwd, bwd-data, bwd-weight timed
+separately with hip events.  Every native row is timed with the resident-
+window route off (HETEROFL_CONV_RESIDENT=0, the staged kernels) and on,
+alternating, in one process; MIOpen (F.conv2d) is the outside reference.
+Run on a GPU box:
+    python scripts/convbench.py [iters] [reps] [--extra]
+`--extra` appends large-window shapes that sit near the resident LDS cap
+(sweep the cap itself with HETEROFL_CONV_RESIDENT_LDS=<bytes>).
 """
+import os
 import sys
 
 import torch
@@ -23,6 +29,11 @@ SHAPES = [
     ('sc2', 5, 10, 64, 32, 128, 1, 2, 0),
     ('sc4', 5, 10, 256, 8, 512, 1, 2, 0),
 ]
+# unsplit slices whose window + tiles need about 53 KB / 64 KB of LDS
+EXTRA = [
+    ('X96', 5, 10, 96, 32, 96, 3, 1, 1),
+    ('X128', 5, 10, 128, 32, 128, 3, 1, 1),
+]
 
 
 def timeit(fn, iters):
@@ -39,14 +50,49 @@ def timeit(fn, iters):
     return s.elapsed_time(e) / iters * 1000  # us
 
 
+def timeit_toggle(fn, iters, reps):
+    """off/on alternating; returns the two lists of per-rep times (us)"""
+    off, on = [], []
+    for _ in range(reps):
+        os.environ['HETEROFL_CONV_RESIDENT'] = '0'
+        off.append(timeit(fn, iters))
+        os.environ['HETEROFL_CONV_RESIDENT'] = '1'
+        on.append(timeit(fn, iters))
+    del os.environ['HETEROFL_CONV_RESIDENT']
+    return off, on
+
+
+def served(dname, H, OH, k, s):
+    """rows whose geometry the staged, hence the resident-window, kernels
+    take: 3x3, whole-row tiles inside one sample (64 pixels fwd/bwd-data,
+    32 bwd-weight); bwd-data stride 1 only.  Slices over the LDS cap still
+    fall back (X128 bwdD)."""
+    if k != 3:
+        return False
+    if dname == 'fwd':
+        return (OH * OH) % 64 == 0 and 64 % OH == 0
+    if dname == 'bwdD':
+        return s == 1 and (H * H) % 64 == 0 and 64 % H == 0
+    return (OH * OH) % 32 == 0 and 32 % OH == 0
+
+
+def med(v):
+    return sorted(v)[len(v) // 2]
+
+
 def main():
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    args = [a for a in sys.argv[1:] if not a.startswith('--')]
+    iters = int(args[0]) if len(args) > 0 else 50
+    reps = int(args[1]) if len(args) > 1 else 5
+    shapes = SHAPES + (EXTRA if '--extra' in sys.argv else [])
     ext = require_native()
     dt = torch.bfloat16
-    print(f'{"shape":6} {"dir":5} {"native_us":>10} {"miopen_us":>10} '
-          f'{"ratio":>6}  gflop')
-    tot_n = tot_m = 0.0
-    for name, G, N, Cin, H, Cout, k, s, p in SHAPES:
+    print(f'{"shape":6} {"dir":5} {"off_us":>8} {"on_us":>8} {"on/off":>6} '
+          f'{"off_spread":>10} {"on_spread":>9} {"res":>3} '
+          f'{"miopen_us":>10} {"ratio":>6}  gflop')
+    tot_n = tot_m = tot_off = 0.0
+    srv_on = srv_off = 0.0
+    for name, G, N, Cin, H, Cout, k, s, p in shapes:
         x = torch.randn(N, G * Cin, H, H, device='cuda', dtype=dt)
         w = torch.randn(G * Cout, Cin, k, k, device='cuda') * 0.1
         wb = w.to(dt)
@@ -68,14 +114,25 @@ def main():
                  x, (G * Cout, Cin, k, k), dy, (s, s), (p, p), (1, 1), G)),
         ]
         for dname, fn_n, fn_m in rows:
-            tn = timeit(fn_n, iters)
+            off, on = timeit_toggle(fn_n, iters, reps)
             tm = timeit(fn_m, iters)
-            tot_n += tn
-            tot_m += tm
-            print(f'{name:6} {dname:5} {tn:10.1f} {tm:10.1f} '
-                  f'{tn / tm:6.2f}  {gflop:.2f}')
-    print(f'TOTAL native {tot_n:.0f}us  miopen {tot_m:.0f}us  '
-          f'ratio {tot_n / tot_m:.2f}')
+            tn, to = med(on), med(off)
+            srv = served(dname, H, OH, k, s)
+            if (name, G, N, Cin, H, Cout, k, s, p) in SHAPES:
+                tot_n += tn
+                tot_off += to
+                tot_m += tm
+                if srv:
+                    srv_on += tn
+                    srv_off += to
+            print(f'{name:6} {dname:5} {to:8.1f} {tn:8.1f} {tn / to:6.2f} '
+                  f'{max(off) - min(off):10.1f} {max(on) - min(on):9.1f} '
+                  f'{"y" if srv else "-":>3} {tm:10.1f} {tn / tm:6.2f}  '
+                  f'{gflop:.2f}')
+    print(f'TOTAL native on {tot_n:.0f}us  off {tot_off:.0f}us  '
+          f'miopen {tot_m:.0f}us  ratio {tot_n / tot_m:.2f}')
+    print(f'RESIDENT rows: on {srv_on:.0f}us  off {srv_off:.0f}us  '
+          f'on/off {srv_on / max(srv_off, 1e-9):.2f}')
 
 
 if __name__ == '__main__':
