@@ -341,9 +341,9 @@ class NativeLMInference:
         for r0 in range(0, h.size(0), step):
             y = label[r0:r0 + step]
             logits = F.linear(h[r0:r0 + step], *self.head_w16)
-            _, lse = self.ext.lm_ce_fwd(
+            lse = self.ext.lm_ce_fwd(
                 logits, y, vocab_mask if vocab_mask is not None
-                else torch.Tensor(), 1)
+                else torch.Tensor(), 1)[1]
             picked = logits.gather(1, y.view(-1, 1)).squeeze(1).float()
             if vocab_mask is not None:
                 picked = picked * (vocab_mask[y] != 0)

@@ -59,7 +59,8 @@ std::vector<at::Tensor> ln_bwd(at::Tensor dy, at::Tensor x, at::Tensor gamma,
 std::vector<at::Tensor> lm_ce_fwd(at::Tensor logits, at::Tensor labels,
                                   at::Tensor mask, int64_t R);
 at::Tensor lm_ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor mask,
-                     at::Tensor row_lse, at::Tensor up, int64_t R);
+                     at::Tensor row_max, at::Tensor row_logsum,
+                     at::Tensor up, int64_t R);
 std::vector<at::Tensor> head_bwd(at::Tensor dscores, at::Tensor pooled,
                                  at::Tensor w, int64_t R, int64_t H,
                                  int64_t W, bool bf16_feat, bool want_db);

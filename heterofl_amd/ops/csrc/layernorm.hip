@@ -19,21 +19,34 @@ ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
     const int l = threadIdx.x & (WAVE - 1);
     const int r = row / rows_per_client;
     const T* xr = x + (long)row * E;
-    float s1 = 0.f, s2 = 0.f;
-    for (int e = l; e < E; e += WAVE) {
-        const float v = ld_f32(xr + e);
-        s1 += v;
-        s2 += v * v;
+    // E <= 1024: a lane owns at most 16 values and keeps them in registers,
+    // so the variance is the mean of (x - mu)^2 after the mean pass.
+    // E[x^2] - mu^2 in fp32 loses mu^2 * 2^-24 absolute, which is the whole
+    // variance once |mean| / std reaches a few hundred.
+    const int ne = (E + WAVE - 1) / WAVE;
+    float xv[16];
+    float s1 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        if (j >= ne) break;
+        const int e = l + j * WAVE;
+        xv[j] = e < E ? ld_f32(xr + e) : 0.f;
+        s1 += xv[j];
     }
-    for (int off = WAVE / 2; off > 0; off >>= 1) {
+    for (int off = WAVE / 2; off > 0; off >>= 1)
         s1 += __shfl_down(s1, off, WAVE);
-        s2 += __shfl_down(s2, off, WAVE);
-    }
-    s1 = __shfl(s1, 0, WAVE);
-    s2 = __shfl(s2, 0, WAVE);
     const float inv_e = 1.f / E;
-    const float mu = s1 * inv_e;
-    const float var = fmaxf(s2 * inv_e - mu * mu, 0.f);
+    const float mu = __shfl(s1, 0, WAVE) * inv_e;
+    float s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        if (j >= ne) break;
+        const float c = l + j * WAVE < E ? xv[j] - mu : 0.f;
+        s2 += c * c;
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1)
+        s2 += __shfl_down(s2, off, WAVE);
+    const float var = __shfl(s2, 0, WAVE) * inv_e;
     const float is = rsqrtf(var + eps);
     if (l == 0) {
         mean_out[row] = mu;
@@ -42,8 +55,12 @@ ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
     T* yr = y + (long)row * E;
     const float* g = gamma + (long)r * E;
     const float* b = beta + (long)r * E;
-    for (int e = l; e < E; e += WAVE)
-        st_f32(yr + e, (ld_f32(xr + e) - mu) * is * g[e] + b[e]);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        if (j >= ne) break;
+        const int e = l + j * WAVE;
+        if (e < E) st_f32(yr + e, (xv[j] - mu) * is * g[e] + b[e]);
+    }
 }
 
 // dx pass; per-row (dgamma, dbeta) contributions go to a (rows, 2, E)

@@ -12,7 +12,8 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 lm_ce_row_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
                  const float* __restrict__ mask, float* __restrict__ row_nll,
-                 float* __restrict__ row_lse, int rows_per_client, int V) {
+                 float* __restrict__ row_lse, float* __restrict__ row_max,
+                 float* __restrict__ row_logsum, int rows_per_client, int V) {
     const int row = blockIdx.x;
     const int r = row / rows_per_client;
     const T* s = logits + (long)row * V;
@@ -50,12 +51,18 @@ lm_ce_row_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
     if (threadIdx.x == 0) {
         float t = 0.f;
         for (int w = 0; w < 256 / WAVE; ++w) t += scratch[w];
-        const float lse = mx + __logf(t);
+        const float logsum = __logf(t);
+        const float lse = mx + logsum;
         const long y = labels[row];
         float vy = ld_f32(s + y);
         if (mk) vy = mk[y] != 0.f ? vy : 0.f;
         row_nll[row] = lse - vy;
         row_lse[row] = lse;
+        // the backward takes the two terms apart: their fp32 sum drops the
+        // low bits of log(sum) once |max| is large (an ulp of 64 is 7.6e-6,
+        // which the softmax would carry as a relative error)
+        row_max[row] = mx;
+        row_logsum[row] = logsum;
     }
 }
 
@@ -75,7 +82,8 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 lm_ce_bwd_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
                  const float* __restrict__ mask,
-                 const float* __restrict__ row_lse,
+                 const float* __restrict__ row_max,
+                 const float* __restrict__ row_logsum,
                  const float* __restrict__ up, T* __restrict__ dlogits,
                  int rows_per_client, int V) {
     const int row = blockIdx.x;
@@ -83,7 +91,8 @@ lm_ce_bwd_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
     const T* s = logits + (long)row * V;
     T* ds = dlogits + (long)row * V;
     const float* mk = mask ? mask + (long)r * V : nullptr;
-    const float lse = row_lse[row];
+    const float mx = row_max[row];
+    const float logsum = row_logsum[row];
     const long y = labels[row];
     const float scale = up[r] / rows_per_client;
     for (int j = threadIdx.x; j < V; j += blockDim.x) {
@@ -91,7 +100,7 @@ lm_ce_bwd_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
         bool live = true;
         if (mk) live = mk[j] != 0.f;
         v = live ? v : 0.f;
-        float g = __expf(v - lse) - (j == y ? 1.f : 0.f);
+        float g = __expf((v - mx) - logsum) - (j == y ? 1.f : 0.f);
         st_f32(ds + j, live ? scale * g : 0.f);
     }
 }
@@ -113,6 +122,8 @@ std::vector<at::Tensor> lm_ce_fwd(at::Tensor logits, at::Tensor labels,
     auto opts = logits.options().dtype(at::kFloat);
     auto row_nll = at::empty({rows}, opts);
     auto row_lse = at::empty({rows}, opts);
+    auto row_max = at::empty({rows}, opts);
+    auto row_logsum = at::empty({rows}, opts);
     auto losses = at::empty({R}, opts);
     auto lab = labels.contiguous();
     auto stream = at::hip::getCurrentHIPStream();
@@ -123,16 +134,19 @@ std::vector<at::Tensor> lm_ce_fwd(at::Tensor logits, at::Tensor labels,
                            lab.data_ptr<long>(),
                            mask.defined() ? mask.data_ptr<float>() : nullptr,
                            row_nll.data_ptr<float>(),
-                           row_lse.data_ptr<float>(), (int)(rows / R), V);
+                           row_lse.data_ptr<float>(),
+                           row_max.data_ptr<float>(),
+                           row_logsum.data_ptr<float>(), (int)(rows / R), V);
     });
     hipLaunchKernelGGL(lm_ce_reduce_kernel, dim3((int)R), dim3(64), 0,
                        stream, row_nll.data_ptr<float>(),
                        losses.data_ptr<float>(), (int)(rows / R));
-    return {losses, row_lse};
+    return {losses, row_lse, row_max, row_logsum};
 }
 
 at::Tensor lm_ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor mask,
-                     at::Tensor row_lse, at::Tensor up, int64_t R) {
+                     at::Tensor row_max, at::Tensor row_logsum,
+                     at::Tensor up, int64_t R) {
     const int V = logits.size(-1);
     const long rows = logits.numel() / V;
     auto dlogits = at::empty_like(logits);
@@ -145,7 +159,8 @@ at::Tensor lm_ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor mask,
                            (const scalar_t*)logits.data_ptr(),
                            lab.data_ptr<long>(),
                            mask.defined() ? mask.data_ptr<float>() : nullptr,
-                           row_lse.data_ptr<float>(),
+                           row_max.data_ptr<float>(),
+                           row_logsum.data_ptr<float>(),
                            upc.data_ptr<float>(),
                            (scalar_t*)dlogits.data_ptr(), (int)(rows / R),
                            V);

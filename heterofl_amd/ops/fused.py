@@ -568,9 +568,9 @@ class _FusedLMCE(torch.autograd.Function):
         ext = require_native()
         logits = logits.contiguous()
         labels = tokens.reshape(-1)
-        losses, row_lse = ext.lm_ce_fwd(
+        losses, _, row_max, row_logsum = ext.lm_ce_fwd(
             logits, labels, mask if mask is not None else torch.Tensor(), R)
-        ctx.save_for_backward(logits, labels, row_lse,
+        ctx.save_for_backward(logits, labels, row_max, row_logsum,
                               mask if mask is not None else torch.Tensor())
         ctx.R = R
         ctx.has_mask = mask is not None
@@ -579,10 +579,10 @@ class _FusedLMCE(torch.autograd.Function):
     @staticmethod
     def backward(ctx, up):
         ext = require_native()
-        logits, labels, row_lse, mask = ctx.saved_tensors
+        logits, labels, row_max, row_logsum, mask = ctx.saved_tensors
         d = ext.lm_ce_bwd(logits, labels,
-                          mask if ctx.has_mask else torch.Tensor(), row_lse,
-                          up, ctx.R)
+                          mask if ctx.has_mask else torch.Tensor(), row_max,
+                          row_logsum, up, ctx.R)
         return d, None, None, None
 
 
