@@ -38,6 +38,10 @@ at::Tensor conv_bwd_data(at::Tensor dy, at::Tensor w, int64_t groups,
 at::Tensor conv_bwd_weight(at::Tensor dy, at::Tensor x, int64_t groups,
                            int64_t stride, int64_t pad, int64_t khw,
                            int64_t fp8);
+std::tuple<std::string, int64_t, int64_t> conv_plan(
+    const std::string& direction, int64_t G, int64_t N, int64_t Cin,
+    int64_t H, int64_t W, int64_t Cout, int64_t khw, int64_t stride,
+    int64_t pad, int64_t elem_size, int64_t fp8);
 at::Tensor mfma_probe(at::Tensor A, at::Tensor B);
 std::vector<at::Tensor> head_fwd(at::Tensor feat, at::Tensor w, at::Tensor b,
                                  int64_t R);
@@ -120,6 +124,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_bwd_data", &conv_bwd_data, "MFMA grouped conv backward-data");
     m.def("conv_bwd_weight", &conv_bwd_weight,
           "MFMA grouped conv backward-weight (fp32 out)");
+    m.def("conv_plan", &conv_plan,
+          "(route, split, dynamic LDS bytes) the conv launchers would take; "
+          "launches nothing");
     m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
     m.def("head_fwd", &head_fwd, "fused avgpool+per-client-linear forward");
     m.def("head_bwd", &head_bwd, "fused head backward");

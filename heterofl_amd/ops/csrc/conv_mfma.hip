@@ -38,6 +38,9 @@
 //             fallback and the bit-exact oracle of the resident kernels.
 //   gather    conv_fwd_kernel, conv_bwd_data{,_s2}_kernel,
 //             conv_bwd_weight_kernel: any geometry, fp8 instantiations.
+// The multi-sample staged fwd / bwd-data kernels and the opt-in switch that
+// selected them measured slower than the gather kernels (profiles/NOTES.md)
+// and were removed; commit 67e6a3a is the last that carries them.
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -163,6 +166,45 @@ struct ConvGeom {
     int stride, pad;
 };
 
+// Where a block and its threads sit, the same in every conv kernel (two
+// spell it out, see there): blockIdx.z = split * G + group; blockIdx.x/y =
+// the 64x64 output tile (row0 = x * BM, col0 = y * BP); each wave owns the
+// 32x32 quadrant (wm, wp) of it.
+struct TileCoord { int g, sp, row0, col0, tid, l, wm, wp; };
+__device__ __forceinline__ TileCoord tile_coord(int G) {
+    TileCoord t;
+    t.g = blockIdx.z % G;
+    t.sp = blockIdx.z / G;
+    t.row0 = blockIdx.x * BM;
+    t.col0 = blockIdx.y * BP;
+    t.tid = threadIdx.x;
+    t.l = t.tid & (WAVE - 1);
+    const int wave = t.tid / WAVE;
+    t.wm = (wave >> 1) * 32;
+    t.wp = (wave & 1) * 32;
+    return t;
+}
+
+// One accumulator element of the fwd epilogue: bias + residual and the cast
+// store when unsplit, else the split's fp32 partial slab (conv_out_reduce
+// applies bias/residual).  ch = g*Cout + m, off = the element's y offset.
+template <typename T>
+__device__ __forceinline__ void fwd_store(float v, long off, int ch,
+                                          const float* __restrict__ bias,
+                                          const T* __restrict__ residual,
+                                          T* __restrict__ y,
+                                          float* __restrict__ partial,
+                                          long slab, int splitk) {
+    if (splitk == 1) {
+        if (bias) v += bias[ch];
+        if (residual) v += ld_f32(residual + off);
+        st_f32(y + off, v);
+    } else {
+        partial[slab + off] = v;
+    }
+}
+
+
 // -------------------------------------------------------------- fwd kernel
 // grid: (ceil(M/BM), ceil(P/BP), G).  Optional residual is added in the
 // epilogue (the ResNet block's `out += shortcut`, src/models/resnet.py:49).
@@ -178,21 +220,16 @@ conv_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
     __shared__ TB b_lds[2][BP][LDK];
     __shared__ int t_ihb[BP], t_iwb[BP];
     __shared__ long t_xbase[BP], t_ybase[BP];
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int m0 = blockIdx.x * BM;
-    const int p0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int m0 = tc.row0, p0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int K = gm.Cin * kk2;
     const int M = gm.Cout;
     const int OHW = gm.OH * gm.OW;
     const int P = gm.N * OHW;
     const int HW = gm.H * gm.W;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
     const int nkc = ((K + BK - 1) / BK + splitk - 1) / splitk;  // BK-chunks
     const int ks = sp * nkc * BK;
     const int ke = min(K, ks + nkc * BK);
@@ -288,17 +325,10 @@ conv_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
-                if (m < M && yb >= 0) {
-                    const long off = yb + (long)m * OHW;
-                    float v = acc[fm][fp][r];
-                    if (splitk == 1) {
-                        if (bias) v += bias[g * gm.Cout + m];
-                        if (residual) v += ld_f32(residual + off);
-                        st_f32(y + off, v);
-                    } else {
-                        partial[slab + off] = v;
-                    }
-                }
+                if (m < M && yb >= 0)
+                    fwd_store(acc[fm][fp][r], yb + (long)m * OHW,
+                              g * gm.Cout + m, bias, residual, y, partial,
+                              slab, splitk);
             }
         }
 }
@@ -329,21 +359,16 @@ conv_bwd_data_kernel(const T* __restrict__ dy, const float* __restrict__ w,
     __shared__ TB b_lds[BP][LDK];
     __shared__ int t_oh[BP], t_ow[BP];  // ih+pad, iw+pad (pre-division)
     __shared__ long t_dybase[BP], t_xbase[BP];
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int c0 = blockIdx.x * BM;
-    const int q0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int c0 = tc.row0, q0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int J = gm.Cout * kk2;
     const int K = gm.Cin * kk2;
     const int HW = gm.H * gm.W;
     const int Q = gm.N * HW;
     const int OHW = gm.OH * gm.OW;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
 
     if (tid < BP) {
         const int q = q0 + tid;
@@ -457,6 +482,8 @@ conv_bwd_data_s2_kernel(const T* __restrict__ dy, const float* __restrict__ w,
     __shared__ TB b_lds[BP][LDK];
     __shared__ int t_oh2[BP], t_ow2[BP];
     __shared__ long t_dybase[BP], t_xbase[BP];
+    // (tile_coord() spelled out: blockIdx.y also carries the parity class,
+    // and going through it reorders this kernel's instructions)
     const int g = blockIdx.z % gm.G;
     const int sp = blockIdx.z / gm.G;
     const int c0 = blockIdx.x * BM;
@@ -595,6 +622,8 @@ conv_bwd_weight_kernel(const T* __restrict__ dy, const T* __restrict__ x,
     __shared__ int t_kcin[BP], t_kkh[BP], t_kkw[BP];   // per-block k tables
     __shared__ int t_ihb[BK], t_iwb[BK];               // per-step p tables
     __shared__ long t_xb[BK], t_dyb[BK];
+    // (tile_coord() spelled out: going through it reorders this kernel's
+    // prologue instructions, and the kernels are held instruction-identical)
     const int g = blockIdx.z % gm.G;
     const int sp = blockIdx.z / gm.G;
     const int m0 = blockIdx.x * BM;
@@ -736,21 +765,16 @@ conv_fwd_staged_kernel(const T* __restrict__ x, const float* __restrict__ w,
     __shared__ TA a_lds[BM][LDK];
     __shared__ TB b_lds[BP][LDK];
     __shared__ float win[WIN_CH][WIN_ROWS][WIN_W];
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int m0 = blockIdx.x * BM;
-    const int p0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int m0 = tc.row0, p0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int K = gm.Cin * kk2;
     const int M = gm.Cout;
     const int OHW = gm.OH * gm.OW;
     const int P = gm.N * OHW;
     const int HW = gm.H * gm.W;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
     const int nkc = ((K + BK - 1) / BK + splitk - 1) / splitk;
     const int ks = sp * nkc * BK;
     const int ke = min(K, ks + nkc * BK);
@@ -850,171 +874,10 @@ conv_fwd_staged_kernel(const T* __restrict__ x, const float* __restrict__ w,
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
-                if (m < M && pp < tile_p) {
-                    const long off = yb0 + pp + (long)m * OHW;
-                    float v = acc[fm][fp][r];
-                    if (splitk == 1) {
-                        if (bias) v += bias[g * gm.Cout + m];
-                        if (residual) v += ld_f32(residual + off);
-                        st_f32(y + off, v);
-                    } else {
-                        partial[slab + off] = v;
-                    }
-                }
-            }
-        }
-}
-
-
-// -------------------------- staged fwd, multi-sample (small output planes)
-// L4-family shapes have OH*OW < BP (e.g. 4x4 = 16 pixels), so a BP tile
-// spans ns = BP/OHW WHOLE samples: stage each sample's full (padded) input
-// plane for the k-slab's channel span and build the B tile from LDS — the
-// same im2col-in-LDS idea as conv_fwd_staged_kernel, which requires
-// OHW %% BP == 0 and therefore left these shapes on the scattered-gather
-// kernel (1.9s of kstats_r02).
-constexpr int MS_ROWS = 40;          // ns * ((OH-1)*stride + khw)
-
-template <typename T, typename TA, typename TB>
-__global__ void __launch_bounds__(256)
-conv_fwd_staged_ms_kernel(const T* __restrict__ x,
-                          const float* __restrict__ w,
-                          const float* __restrict__ bias,
-                          const T* __restrict__ residual, T* __restrict__ y,
-                          float* __restrict__ partial, ConvGeom gm,
-                          int splitk) {
-    __shared__ TA a_lds[BM][LDK];
-    __shared__ TB b_lds[BP][LDK];
-    __shared__ float win[WIN_CH][MS_ROWS][WIN_W];
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int m0 = blockIdx.x * BM;
-    const int p0 = blockIdx.y * BP;
-    const int kk2 = gm.khw * gm.khw;
-    const int K = gm.Cin * kk2;
-    const int M = gm.Cout;
-    const int OHW = gm.OH * gm.OW;
-    const int P = gm.N * OHW;
-    const int HW = gm.H * gm.W;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
-    const int nkc = ((K + BK - 1) / BK + splitk - 1) / splitk;
-    const int ks = sp * nkc * BK;
-    const int ke = min(K, ks + nkc * BK);
-    // tile geometry: ns whole samples, full output planes
-    const int ns = BP / OHW;
-    const int n0 = p0 / OHW;
-    const int rows_in = (gm.OH - 1) * gm.stride + gm.khw;
-    const long gch = ((long)g * gm.Cin) * HW;
-    const long sampstride = (long)gm.G * gm.Cin * HW;
-    const int tile_p = min(BP, P - p0);
-    const int mm_a = tid >> 2, kkb = (tid & 3) * 8;
-    const int pp_b = tid >> 2;
-    const int ls_b = pp_b / OHW;
-    const int pix_b = pp_b - ls_b * OHW;
-    const int ohl_b = (pix_b / gm.OW) * gm.stride;
-    const int iwl_b = (pix_b - (pix_b / gm.OW) * gm.OW) * gm.stride;
-    const int rowb_b = ls_b * rows_in;
-    float va[8];
-
-    f32x4 acc[2][2] = {};
-    for (int k0 = ks; k0 < ke; k0 += BK) {
-        const int cin0 = k0 / kk2;
-        const int cin1 = min(gm.Cin - 1, (k0 + BK - 1) / kk2);
-        const int nch = cin1 - cin0 + 1;
-        // stage ns sample planes (coalesced along the input width)
-        const int wtot = nch * ns * rows_in * gm.W;
-        for (int e = tid; e < wtot; e += 256) {
-            const int ww = e % gm.W;
-            const int rr = (e / gm.W) % rows_in;
-            const int lsl = (e / (gm.W * rows_in)) % ns;
-            const int cc = e / (gm.W * rows_in * ns);
-            const int ih = rr - gm.pad;
-            const int n = n0 + lsl;
-            win[cc][lsl * rows_in + rr][ww + gm.pad] =
-                (ih >= 0 && ih < gm.H && n < gm.N)
-                    ? ld_f32(x + (long)n * sampstride + gch
-                             + (long)(cin0 + cc) * HW + ih * gm.W + ww)
-                    : 0.f;
-        }
-        for (int e = tid; e < nch * ns * rows_in * gm.pad * 2; e += 256) {
-            const int side = e & 1;
-            const int pe = e >> 1;
-            const int pcol = pe % gm.pad;
-            const int rr = (pe / gm.pad) % (ns * rows_in);
-            const int cc = pe / (gm.pad * ns * rows_in);
-            win[cc][rr][side ? gm.pad + gm.W + pcol : pcol] = 0.f;
-        }
-        {   // A tile (weights, coalesced fp32)
-            const int m = m0 + mm_a;
-            const float* wrow = w + (long)(g * gm.Cout + m) * K + k0 + kkb;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = k0 + kkb + j;
-                va[j] = (m < M && k < K) ? wrow[j] : 0.f;
-            }
-            st8_lds(&a_lds[mm_a][kkb], va);
-        }
-        __syncthreads();
-        {   // B tile from the LDS windows
-            float vb[8];
-            int k = k0 + kkb;
-            int cin = k / kk2, r = k - cin * kk2;
-            int kh = r / gm.khw, kw = r - kh * gm.khw;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                vb[j] = (k + j < K && pp_b < tile_p)
-                            ? win[cin - cin0][rowb_b + ohl_b + kh]
-                                 [iwl_b + kw]
-                            : 0.f;
-                if (++kw == gm.khw) {
-                    kw = 0;
-                    if (++kh == gm.khw) {
-                        kh = 0;
-                        ++cin;
-                    }
-                }
-            }
-            st8_lds(&b_lds[pp_b][kkb], vb);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int fm = 0; fm < 2; ++fm)
-#pragma unroll
-            for (int fp = 0; fp < 2; ++fp)
-                acc[fm][fp] = mfma_tile2<TA, TB>(
-                    &a_lds[wm + fm * 16 + (l & 15)][0],
-                    &b_lds[wp + fp * 16 + (l & 15)][0], acc[fm][fp]);
-        __syncthreads();
-    }
-    const long slab = (long)sp * gm.N * gm.G * gm.Cout * OHW;
-    const long ystride = (long)gm.G * gm.Cout * OHW;
-    const long ygch = (long)g * gm.Cout * OHW;
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm)
-#pragma unroll
-        for (int fp = 0; fp < 2; ++fp) {
-            const int pp = wp + fp * 16 + (l & 15);
-            const int lsl = pp / OHW;
-            const int pix = pp - lsl * OHW;
-            const long yb = (long)(n0 + lsl) * ystride + ygch + pix;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
-                if (m < M && pp < tile_p) {
-                    const long off = yb + (long)m * OHW;
-                    float v = acc[fm][fp][r];
-                    if (splitk == 1) {
-                        if (bias) v += bias[g * gm.Cout + m];
-                        if (residual) v += ld_f32(residual + off);
-                        st_f32(y + off, v);
-                    } else {
-                        partial[slab + off] = v;
-                    }
-                }
+                if (m < M && pp < tile_p)
+                    fwd_store(acc[fm][fp][r], yb0 + pp + (long)m * OHW,
+                              g * gm.Cout + m, bias, residual, y, partial,
+                              slab, splitk);
             }
         }
 }
@@ -1032,20 +895,15 @@ conv_bwd_data_staged_kernel(const T* __restrict__ dy,
     __shared__ TA a_lds[BM][LDK];
     __shared__ TB b_lds[BP][LDK];
     __shared__ float win[WIN_CH][WIN_ROWS][WIN_W];
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int c0 = blockIdx.x * BM;
-    const int q0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int c0 = tc.row0, q0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int J = gm.Cout * kk2;
     const int K = gm.Cin * kk2;
     const int HW = gm.H * gm.W;
     const int OHW = gm.OH * gm.OW;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
     const int njc = ((J + BK - 1) / BK + splitk - 1) / splitk;
     const int js = sp * njc * BK;
     const int je = min(J, js + njc * BK);
@@ -1166,161 +1024,6 @@ conv_bwd_data_staged_kernel(const T* __restrict__ dy,
         }
 }
 
-
-// ------------------- staged stride-1 bwd-data, multi-sample (small planes)
-// Same extension as conv_fwd_staged_ms_kernel: a BP-pixel dx tile spanning
-// BP/HW whole samples stages each sample's full padded dy plane per J-step.
-template <typename T, typename TA, typename TB>
-__global__ void __launch_bounds__(256)
-conv_bwd_data_staged_ms_kernel(const T* __restrict__ dy,
-                               const float* __restrict__ w,
-                               T* __restrict__ dx,
-                               float* __restrict__ partial, ConvGeom gm,
-                               int splitk) {
-    __shared__ TA a_lds[BM][LDK];
-    __shared__ TB b_lds[BP][LDK];
-    __shared__ float win[WIN_CH][MS_ROWS][WIN_W];
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int c0 = blockIdx.x * BM;
-    const int q0 = blockIdx.y * BP;
-    const int kk2 = gm.khw * gm.khw;
-    const int J = gm.Cout * kk2;
-    const int K = gm.Cin * kk2;
-    const int HW = gm.H * gm.W;
-    const int OHW = gm.OH * gm.OW;
-    const int Q = gm.N * HW;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
-    const int njc = ((J + BK - 1) / BK + splitk - 1) / splitk;
-    const int js = sp * njc * BK;
-    const int je = min(J, js + njc * BK);
-    const int ns = BP / HW;
-    const int n0 = q0 / HW;
-    // dy rows needed for a full dx plane: ohs = ih + pad - kh over ih in
-    // [0, H) -> rows [pad - (khw-1), H - 1 + pad]; stage rows_w rows from
-    // ohs_min with zero-fill outside [0, OH)
-    const int rows_w = gm.H + gm.khw - 1;
-    const int ohs_min = gm.pad - (gm.khw - 1);
-    const long dgch = (long)g * gm.Cout * OHW;
-    const long dystride = (long)gm.G * gm.Cout * OHW;
-    const int tile_q = min(BP, Q - q0);
-    const int cc_a = tid >> 2, jjb = (tid & 3) * 8;
-    const int ls_b = cc_a / HW;
-    const int pix_b = cc_a - ls_b * HW;
-    const int iwl = pix_b - (pix_b / gm.W) * gm.W;
-    const int rowl = (pix_b / gm.W) + (gm.khw - 1);
-    const int rowb = ls_b * rows_w;
-    float va[8];
-
-    f32x4 acc[2][2] = {};
-    for (int j0 = js; j0 < je; j0 += BK) {
-        const int co0 = j0 / kk2;
-        const int co1 = min(gm.Cout - 1, (j0 + BK - 1) / kk2);
-        const int nch = co1 - co0 + 1;
-        const int wtot = nch * ns * rows_w * gm.OW;
-        for (int e = tid; e < wtot; e += 256) {
-            const int ww = e % gm.OW;
-            const int rr = (e / gm.OW) % rows_w;
-            const int lsl = (e / (gm.OW * rows_w)) % ns;
-            const int cc = e / (gm.OW * rows_w * ns);
-            const int ohs = ohs_min + rr;
-            const int n = n0 + lsl;
-            win[cc][lsl * rows_w + rr][ww + gm.pad] =
-                (ohs >= 0 && ohs < gm.OH && n < gm.N)
-                    ? ld_f32(dy + (long)n * dystride + dgch
-                             + (long)(co0 + cc) * OHW + ohs * gm.OW + ww)
-                    : 0.f;
-        }
-        for (int e = tid; e < nch * ns * rows_w * gm.pad * 2; e += 256) {
-            const int side = e & 1;
-            const int pe = e >> 1;
-            const int pcol = pe % gm.pad;
-            const int rr = (pe / gm.pad) % (ns * rows_w);
-            const int cc = pe / (gm.pad * ns * rows_w);
-            win[cc][rr][side ? gm.pad + gm.OW + pcol : pcol] = 0.f;
-        }
-        {   // A tile: w rows = input channel
-            const int c = c0 + cc_a;
-            int j = j0 + jjb;
-            int cout = j / kk2, r = j - cout * kk2;
-            int kh = r / gm.khw, kw = r - kh * gm.khw;
-#pragma unroll
-            for (int j8 = 0; j8 < 8; ++j8) {
-                va[j8] = (c < gm.Cin && j + j8 < J)
-                             ? w[(long)(g * gm.Cout + cout) * K + c * kk2
-                                 + kh * gm.khw + kw]
-                             : 0.f;
-                if (++kw == gm.khw) {
-                    kw = 0;
-                    if (++kh == gm.khw) {
-                        kh = 0;
-                        ++cout;
-                    }
-                }
-            }
-            st8_lds(&a_lds[cc_a][jjb], va);
-        }
-        __syncthreads();
-        {   // B tile from the windows
-            float vb[8];
-            int j = j0 + jjb;
-            int cout = j / kk2, r = j - cout * kk2;
-            int kh = r / gm.khw, kw = r - kh * gm.khw;
-#pragma unroll
-            for (int j8 = 0; j8 < 8; ++j8) {
-                vb[j8] = (j + j8 < J && cc_a < tile_q)
-                             ? win[cout - co0][rowb + rowl - kh]
-                                  [iwl + 2 * gm.pad - kw]
-                             : 0.f;
-                if (++kw == gm.khw) {
-                    kw = 0;
-                    if (++kh == gm.khw) {
-                        kh = 0;
-                        ++cout;
-                    }
-                }
-            }
-            st8_lds(&b_lds[cc_a][jjb], vb);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int fm = 0; fm < 2; ++fm)
-#pragma unroll
-            for (int fp = 0; fp < 2; ++fp)
-                acc[fm][fp] = mfma_tile2<TA, TB>(
-                    &a_lds[wm + fm * 16 + (l & 15)][0],
-                    &b_lds[wp + fp * 16 + (l & 15)][0], acc[fm][fp]);
-        __syncthreads();
-    }
-    const long slab = (long)sp * gm.N * gm.G * gm.Cin * HW;
-    const long xstride = (long)gm.G * gm.Cin * HW;
-    const long xgch = (long)g * gm.Cin * HW;
-#pragma unroll
-    for (int fm = 0; fm < 2; ++fm)
-#pragma unroll
-        for (int fp = 0; fp < 2; ++fp) {
-            const int qq = wp + fp * 16 + (l & 15);
-            const int lsl = qq / HW;
-            const int pix = qq - lsl * HW;
-            const long xb = (long)(n0 + lsl) * xstride + xgch + pix;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = c0 + wm + fm * 16 + (l >> 4) * 4 + r;
-                if (c < gm.Cin && qq < tile_q) {
-                    const long off = xb + (long)c * HW;
-                    if (splitk == 1)
-                        st_f32(dx + off, acc[fm][fp][r]);
-                    else
-                        partial[slab + off] = acc[fm][fp][r];
-                }
-            }
-        }
-}
-
 // -------------------------------------- staged bwd-weight (x window in LDS)
 // The k-tile (hence the input-channel span) is FIXED per block, so the x
 // window only advances rows as the P loop walks output rows: stage the
@@ -1338,21 +1041,16 @@ conv_bwd_weight_staged_kernel(const T* __restrict__ dy,
     __shared__ TB b_lds[BP][LDK];
     __shared__ float win[WWIN_CH][WIN_ROWS][WIN_W];
     __shared__ long t_dyb[BK];
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int m0 = blockIdx.x * BM;
-    const int k0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int m0 = tc.row0, k0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int K = gm.Cin * kk2;
     const int M = gm.Cout;
     const int OHW = gm.OH * gm.OW;
     const int P = gm.N * OHW;
     const int HW = gm.H * gm.W;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
     const int pchunk0 = (P + splitp - 1) / splitp;
     const int pchunk = ((pchunk0 + BK - 1) / BK) * BK;  // BK-aligned chunks
     const int pstart = sp * pchunk;
@@ -1550,20 +1248,15 @@ conv_fwd_resident_kernel(const T* __restrict__ x, const float* __restrict__ w,
     __shared__ T b_lds[2][BP][LDK];
     R* win = (R*)dyn_lds;
     unsigned short* koff = (unsigned short*)(dyn_lds + tab_bytes);
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int m0 = blockIdx.x * BM;
-    const int p0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int m0 = tc.row0, p0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int K = gm.Cin * kk2;
     const int M = gm.Cout;
     const int OHW = gm.OH * gm.OW;
     const int HW = gm.H * gm.W;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
     const int nkc = ((K + BK - 1) / BK + splitk - 1) / splitk;
     const int ks = sp * nkc * BK;
     const int ke = min(K, ks + nkc * BK);
@@ -1671,17 +1364,10 @@ conv_fwd_resident_kernel(const T* __restrict__ x, const float* __restrict__ w,
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
-                if (m < M) {
-                    const long off = yb0 + pp + (long)m * OHW;
-                    float v = acc[fm][fp][r];
-                    if (splitk == 1) {
-                        if (bias) v += bias[g * gm.Cout + m];
-                        if (residual) v += ld_f32(residual + off);
-                        st_f32(y + off, v);
-                    } else {
-                        partial[slab + off] = v;
-                    }
-                }
+                if (m < M)
+                    fwd_store(acc[fm][fp][r], yb0 + pp + (long)m * OHW,
+                              g * gm.Cout + m, bias, residual, y, partial,
+                              slab, splitk);
             }
         }
 }
@@ -1705,20 +1391,15 @@ conv_bwd_data_resident_kernel(const T* __restrict__ dy,
     R* win = (R*)dyn_lds;
     int* woff = (int*)(dyn_lds + woff_bytes);
     unsigned short* joff = (unsigned short*)(dyn_lds + joff_bytes);
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int c0 = blockIdx.x * BM;
-    const int q0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int c0 = tc.row0, q0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int J = gm.Cout * kk2;
     const int K = gm.Cin * kk2;
     const int HW = gm.H * gm.W;
     const int OHW = gm.OH * gm.OW;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
     const int njc = ((J + BK - 1) / BK + splitk - 1) / splitk;
     const int js = sp * njc * BK;
     const int je = min(J, js + njc * BK);
@@ -1888,21 +1569,16 @@ conv_bwd_weight_resident_kernel(const T* __restrict__ dy,
     __shared__ T a_lds[2][BM][LDK];
     __shared__ T b_lds[2][BP][LDK];
     R* win = (R*)dyn_lds;
-    const int g = blockIdx.z % gm.G;
-    const int sp = blockIdx.z / gm.G;
-    const int m0 = blockIdx.x * BM;
-    const int k0 = blockIdx.y * BP;
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int m0 = tc.row0, k0 = tc.col0;
     const int kk2 = gm.khw * gm.khw;
     const int K = gm.Cin * kk2;
     const int M = gm.Cout;
     const int OHW = gm.OH * gm.OW;
     const int P = gm.N * OHW;
     const int HW = gm.H * gm.W;
-    const int tid = threadIdx.x;
-    const int l = tid & (WAVE - 1);
-    const int wave = tid / WAVE;
-    const int wm = (wave >> 1) * 32;
-    const int wp = (wave & 1) * 32;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
     const int pchunk0 = (P + splitp - 1) / splitp;
     const int pchunk = ((pchunk0 + BK - 1) / BK) * BK;  // BK-aligned chunks
     const int pstart = sp * pchunk;
@@ -2016,11 +1692,19 @@ conv_bwd_weight_resident_kernel(const T* __restrict__ dy,
 }
 
 // ------------------------------------------------------------ host layer
+// Deciding is separate from launching.  plan_fwd / plan_bwd_data /
+// plan_bwd_weight are pure functions of (geometry, element size, fp8 flag)
+// and the HETEROFL_CONV_* switches; each conv_* entry point below selects a
+// kernel from its plan and launches once.  conv_plan() hands the same plans
+// to Python so a test can pin which kernel and split a shape takes.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <string>
+#include <tuple>
+#include <type_traits>
 
 // target concurrent-block count for the split-K/split-P decompositions
 // (tunable: HETEROFL_CONV_SPLIT_TARGET, default 1024 = 4 blocks/CU)
@@ -2056,11 +1740,12 @@ static int resident_lds_cap() {
 static bool aligned16(const void* p) {
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
-// LDS plan of one resident launch (bytes); chunks = BK-chunks per slice,
-// tap2 = khw*khw, nchan = channels of the staged tensor, width = its row
-static bool resident_plan(int chunks, int tap2, int nchan, int rows,
-                          int width, int esz, int tab_entry_bytes,
-                          int* win_bytes) {
+// LDS need of one resident fwd / bwd-data launch (bytes); chunks =
+// BK-chunks per slice, tap2 = khw*khw, nchan = channels of the staged
+// tensor, width = its row
+static bool resident_window_fits(int chunks, int tap2, int nchan, int rows,
+                                 int width, int esz, int tab_entry_bytes,
+                                 int* win_bytes) {
     const int nch_max = std::min(nchan, (chunks * BK - 1) / tap2 + 2);
     const long welems = (long)nch_max * rows * (width + WGAP) + WGAP;
     if (welems >= 65536) return false;   // ushort offsets
@@ -2070,172 +1755,275 @@ static bool resident_plan(int chunks, int tap2, int nchan, int rows,
            <= resident_lds_cap();
 }
 
+static int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+static ConvGeom conv_geom(int64_t G, int64_t N, int64_t Cin, int64_t H,
+                          int64_t W, int64_t Cout, int64_t khw,
+                          int64_t stride, int64_t pad) {
+    ConvGeom gm;
+    gm.G = (int)G;
+    gm.N = (int)N;
+    gm.H = (int)H;
+    gm.W = (int)W;
+    gm.Cin = (int)Cin;
+    gm.Cout = (int)Cout;
+    gm.khw = (int)khw;
+    gm.stride = (int)stride;
+    gm.pad = (int)pad;
+    TORCH_CHECK(gm.khw > 0 && gm.stride > 0 && gm.H + 2 * gm.pad >= gm.khw
+                && gm.W + 2 * gm.pad >= gm.khw, "bad conv geometry");
+    gm.OH = (gm.H + 2 * gm.pad - gm.khw) / gm.stride + 1;
+    gm.OW = (gm.W + 2 * gm.pad - gm.khw) / gm.stride + 1;
+    return gm;
+}
+
+enum Route { GATHER, GATHER_S2, STAGED, RESIDENT };
+
+struct ConvPlan {
+    Route route;
+    bool fp8;       // gather kernels only: the e4m3/e5m2 tile instantiation
+    int split;      // split-K (fwd, bwd-data) or split-P (bwd-weight)
+    dim3 grid;
+    int dyn_lds;    // resident launch: dynamic LDS bytes
+    int tab0, tab1; // resident launch: byte offsets of its tables in there
+    int nyp;        // gather_s2: pixel tiles per parity class
+};
+
+// Split of the fwd (K) and bwd-data (J) reduction over `tiles` output
+// tiles.  Same rule as bwdW (measured, L3): short reductions with enough
+// tiles run best unsplit — the split's partial-write + reduce traffic beats
+// the extra parallelism.
+static int split_reduction(int red, int tiles) {
+    const int chunks = cdiv(red, BK);
+    int split = 1;
+    if (red > 1024 || tiles < 512)
+        while (tiles * split < split_target() && split * 2 <= chunks / 2)
+            split *= 2;
+    return split;
+}
+
+// fp8 tiles exist for bf16 tensors only (esz == 2).  With fp8 set on fp32
+// tensors the directions differ, and that is kept as it always was: fwd
+// leaves the window kernels for the plain fp32 gather kernel, bwd-data
+// leaves only the resident kernel (for the staged one), bwd-weight ignores
+// the flag.
+static ConvPlan plan_fwd(const ConvGeom& gm, int esz, bool fp8) {
+    const int tap2 = gm.khw * gm.khw;
+    const int K = gm.Cin * tap2;
+    const int OHW = gm.OH * gm.OW;
+    const int P = gm.N * OHW;
+    const int mt = cdiv(gm.Cout, BM), pt = cdiv(P, BP);
+    ConvPlan pl = {};
+    pl.split = split_reduction(K, mt * pt * gm.G);
+    pl.grid = dim3(mt, pt, gm.G * pl.split);
+    const bool staged = !fp8 && (P % BP == 0 || P >= BP) && OHW % BP == 0
+                        && BP % gm.OW == 0
+                        && (gm.W + 2 * gm.pad) <= WIN_W - 2
+                        && ((BP / gm.OW - 1) * gm.stride + gm.khw) <= WIN_ROWS
+                        && (BK / tap2 + 2) <= WIN_CH;
+    // resident window: wherever the staged kernel is routed and the slice's
+    // window fits under the LDS cap
+    const int nkc = cdiv(cdiv(K, BK), pl.split);
+    int win_bytes = 0;
+    if (staged && resident_on() && P % BP == 0 && 2 * gm.pad <= WGAP
+        && resident_window_fits(nkc, tap2, gm.Cin,
+                                (BP / gm.OW - 1) * gm.stride + gm.khw, gm.W,
+                                esz, 2, &win_bytes)) {
+        pl.route = RESIDENT;
+        pl.tab0 = win_bytes;                     // ushort k-offset table
+        pl.dyn_lds = win_bytes + nkc * BK * 2;
+    } else if (staged) {
+        pl.route = STAGED;
+    } else {
+        pl.route = GATHER;
+        pl.fp8 = fp8 && esz == 2;
+    }
+    return pl;
+}
+
+static ConvPlan plan_bwd_data(const ConvGeom& gm, int esz, bool fp8) {
+    const int tap2 = gm.khw * gm.khw;
+    const int Q = gm.N * gm.H * gm.W;
+    const bool s2 = (gm.stride == 2 && gm.H % 2 == 0 && gm.W % 2 == 0);
+    // parity path: 4 classes of Q/4 pixels, ~1/4 the taps each
+    const int Jfull = gm.Cout * tap2;
+    const int J = s2 ? (Jfull + 3) / 4 : Jfull;
+    const int ct = cdiv(gm.Cin, BM);
+    ConvPlan pl = {};
+    pl.nyp = cdiv(s2 ? Q / 4 : Q, BP);
+    const int qt = pl.nyp * (s2 ? 4 : 1);
+    pl.split = split_reduction(J, ct * qt * gm.G);
+    pl.grid = dim3(ct, qt, gm.G * pl.split);
+    const bool q = fp8 && esz == 2;
+    const bool staged = !q && !s2 && gm.stride == 1
+                        && (gm.H * gm.W) % BP == 0 && BP % gm.W == 0
+                        && (gm.OW + 2 * gm.pad) <= WIN_W - 2
+                        && (BP / gm.W + gm.khw - 1) <= WIN_ROWS
+                        && (BK / tap2 + 2) <= WIN_CH;
+    // resident dy window (2*pad >= khw-1: the geometry the staged kernel's
+    // own window addressing covers)
+    const int njc = cdiv(cdiv(J, BK), pl.split);
+    int win_bytes = 0;
+    if (staged && !fp8 && resident_on() && 2 * gm.pad <= WGAP
+        && 2 * gm.pad >= gm.khw - 1
+        && resident_window_fits(njc, tap2, gm.Cout, BP / gm.W + gm.khw - 1,
+                                gm.OW, esz, 6, &win_bytes)) {
+        pl.route = RESIDENT;
+        pl.tab0 = win_bytes;                     // int weight-offset table
+        pl.tab1 = win_bytes + njc * BK * 4;      // ushort window-offset table
+        pl.dyn_lds = win_bytes + njc * BK * 6;
+    } else if (staged) {
+        pl.route = STAGED;
+    } else {
+        pl.route = s2 ? GATHER_S2 : GATHER;
+        pl.fp8 = q;
+    }
+    return pl;
+}
+
+static ConvPlan plan_bwd_weight(const ConvGeom& gm, int esz, bool fp8) {
+    const int K = gm.Cin * gm.khw * gm.khw;
+    const int OHW = gm.OH * gm.OW;
+    const int P = gm.N * OHW;
+    const int mt = cdiv(gm.Cout, BM), kt = cdiv(K, BP);
+    const int mk_tiles = mt * kt * gm.G;
+    ConvPlan pl = {};
+    pl.split = 1;
+    // measured (bwdw2 r2): small-P shapes that already have >=512 (m,k)
+    // tiles need no split at all — L3 bwdW 89.4us (splitp 2) -> 74.5us
+    // (splitp 1) = 1.00x MIOpen; splitting only pays when tiles are scarce
+    // or P is long enough to amortize the partial reduce
+    if (P > 1024 || mk_tiles < 512)
+        while (mk_tiles * pl.split < split_target()
+               && pl.split * BK * 4 < P)
+            pl.split *= 2;
+    pl.grid = dim3(mt, kt, gm.G * pl.split);
+    const bool q = fp8 && esz == 2;
+    // staged path: 3x3 kernels (a 64-wide k-tile then spans <= 9 input
+    // channels = WWIN_CH), p-steps inside one sample spanning whole rows
+    const bool staged = !q && gm.khw == 3 && OHW % BK == 0 && BK % gm.OW == 0
+                        && (gm.W + 2 * gm.pad) <= WIN_W - 2
+                        && ((BK / gm.OW - 1) * gm.stride + gm.khw) <= WIN_ROWS;
+    if (!staged) {
+        pl.route = GATHER;
+        pl.fp8 = q;
+        return pl;
+    }
+    // resident x window: one sample segment of the p-chunk at a time
+    const int pchunk = cdiv(cdiv(P, pl.split), BK) * BK;
+    const long wwin = (long)std::min(gm.Cin, WWIN_CH)
+                          * ((std::min(pchunk, OHW) / gm.OW - 1) * gm.stride
+                             + gm.khw) * (gm.W + WGAP) + WGAP;
+    if (resident_on() && 2 * gm.pad <= WGAP
+        && 2L * (BM + BP) * LDK * esz + wwin * esz <= resident_lds_cap()) {
+        pl.route = RESIDENT;
+        pl.dyn_lds = (int)((wwin * esz + 15) / 16 * 16);
+    } else {
+        pl.route = STAGED;
+    }
+    return pl;
+}
+
+std::tuple<std::string, int64_t, int64_t> conv_plan(
+        const std::string& direction, int64_t G, int64_t N, int64_t Cin,
+        int64_t H, int64_t W, int64_t Cout, int64_t khw, int64_t stride,
+        int64_t pad, int64_t elem_size, int64_t fp8) {
+    TORCH_CHECK(elem_size == 2 || elem_size == 4, "elem_size must be 2 or 4");
+    const ConvGeom gm = conv_geom(G, N, Cin, H, W, Cout, khw, stride, pad);
+    ConvPlan pl;
+    if (direction == "fwd")
+        pl = plan_fwd(gm, (int)elem_size, fp8 != 0);
+    else if (direction == "bwd_data")
+        pl = plan_bwd_data(gm, (int)elem_size, fp8 != 0);
+    else if (direction == "bwd_weight")
+        pl = plan_bwd_weight(gm, (int)elem_size, fp8 != 0);
+    else
+        TORCH_CHECK(false, "direction must be fwd, bwd_data or bwd_weight");
+    static const char* const names[] = {"gather", "gather_s2", "staged",
+                                        "resident"};
+    return {std::string(names[pl.route]) + (pl.fp8 ? "_fp8" : ""), pl.split,
+            pl.dyn_lds};
+}
+
 #define DISPATCH_CONV_FT(t, ...)                                              \
     if ((t) == at::kFloat) { using scalar_t = float; __VA_ARGS__; }           \
     else if ((t) == at::kBFloat16) { using scalar_t = __hip_bfloat16; __VA_ARGS__; } \
     else { TORCH_CHECK(false, "unsupported dtype"); }
+
+// The non-resident kernels of a direction share a signature: pick by plan.
+// fp8 tiles are instantiated for bf16 tensors only.
+template <typename T>
+static auto fwd_kernel(const ConvPlan& pl) {
+    if (pl.route == STAGED) return conv_fwd_staged_kernel<T, T, T>;
+    if constexpr (std::is_same<T, __hip_bfloat16>::value)
+        if (pl.fp8) return conv_fwd_kernel<T, e4m3, e4m3>;
+    return conv_fwd_kernel<T, T, T>;
+}
+template <typename T>
+static auto bwd_data_kernel(const ConvPlan& pl) {
+    if (pl.route == STAGED) return conv_bwd_data_staged_kernel<T, T, T>;
+    if constexpr (std::is_same<T, __hip_bfloat16>::value)
+        if (pl.fp8) return conv_bwd_data_kernel<T, e4m3, e5m2>;
+    return conv_bwd_data_kernel<T, T, T>;
+}
+template <typename T>
+static auto bwd_data_s2_kernel(const ConvPlan& pl) {
+    if constexpr (std::is_same<T, __hip_bfloat16>::value)
+        if (pl.fp8) return conv_bwd_data_s2_kernel<T, e4m3, e5m2>;
+    return conv_bwd_data_s2_kernel<T, T, T>;
+}
+template <typename T>
+static auto bwd_weight_kernel(const ConvPlan& pl) {
+    if (pl.route == STAGED) return conv_bwd_weight_staged_kernel<T, T, T>;
+    if constexpr (std::is_same<T, __hip_bfloat16>::value)
+        if (pl.fp8) return conv_bwd_weight_kernel<T, e5m2, e4m3>;
+    return conv_bwd_weight_kernel<T, T, T>;
+}
 
 at::Tensor conv_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
                     at::Tensor residual, int64_t groups, int64_t stride,
                     int64_t pad, int64_t fp8) {
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && w.is_contiguous());
     TORCH_CHECK(w.scalar_type() == at::kFloat, "weights must be fp32 master");
-    ConvGeom gm;
-    gm.G = (int)groups;
-    gm.N = x.size(0);
-    gm.H = x.size(2);
-    gm.W = x.size(3);
-    gm.Cin = (int)w.size(1);
-    gm.Cout = (int)(w.size(0) / groups);
-    gm.khw = (int)w.size(2);
-    gm.stride = (int)stride;
-    gm.pad = (int)pad;
-    gm.OH = (gm.H + 2 * gm.pad - gm.khw) / gm.stride + 1;
-    gm.OW = (gm.W + 2 * gm.pad - gm.khw) / gm.stride + 1;
-    auto y = at::empty({gm.N, gm.G * gm.Cout, gm.OH, gm.OW}, x.options());
-    const int M = gm.Cout, P = gm.N * gm.OH * gm.OW;
-    const int K = gm.Cin * gm.khw * gm.khw;
-    const int kchunks = (K + BK - 1) / BK;
-    const int tiles = ((M + BM - 1) / BM) * ((P + BP - 1) / BP) * gm.G;
-    int splitk = 1;
-    // same rule as bwdW (measured, L3): short reductions with enough tiles
-    // run best unsplit — the split's partial-write + reduce traffic beats
-    // the extra parallelism (HETEROFL_SPLIT_NOSKIP=1 restores the old
-    // always-split heuristic for A/B)
-    static const bool noskip_f = [] {
-        const char* e = std::getenv("HETEROFL_SPLIT_NOSKIP");
-        return e && e[0] == '1';
-    }();
-    if (noskip_f || K > 1024 || tiles < 512)
-        while (tiles * splitk < split_target() && splitk * 2 <= kchunks / 2)
-            splitk *= 2;
-    dim3 grid((M + BM - 1) / BM, (P + BP - 1) / BP, gm.G * splitk);
-    auto stream = at::hip::getCurrentHIPStream();
-    at::Tensor partial;
-    if (splitk > 1)
-        partial = at::empty({(long)splitk * y.numel()},
-                            x.options().dtype(at::kFloat));
-    const int OHW = gm.OH * gm.OW;
-    const bool staged = (P % BP == 0 || gm.N * gm.OH * gm.OW >= BP)
-                        && (gm.OH * gm.OW) % BP == 0 && BP % gm.OW == 0
-                        && (gm.W + 2 * gm.pad) <= WIN_W - 2
-                        && ((BP / gm.OW - 1) * gm.stride + gm.khw) <= WIN_ROWS
-                        && (BK / (gm.khw * gm.khw) + 2) <= WIN_CH
-                        && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
-    // small output planes: a BP tile spans BP/OHW whole samples.
-    // MEASURED NEGATIVE at the training shapes (convbench r02c: L4 fwd
-    // 107->124us, L4d 67->101us — the 32 KB window slab costs more
-    // occupancy than the gather kernel loses to scattered loads); kept
-    // opt-in for future large-batch study
-    static const bool ms_on = [] {
-        const char* e = std::getenv("HETEROFL_CONV_MS");
-        return e && e[0] == '1';
-    }();
-    const bool staged_ms = ms_on && !staged && OHW < BP && BP % OHW == 0
-                          && (gm.W + 2 * gm.pad) <= WIN_W - 2
-                          && (BP / OHW) * ((gm.OH - 1) * gm.stride + gm.khw)
-                                 <= MS_ROWS
-                          && (BK / (gm.khw * gm.khw) + 2) <= WIN_CH
-                          && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
-    // resident window: wherever the staged kernel is routed and the slice's
-    // window fits under the LDS cap
+    const ConvGeom gm = conv_geom(groups, x.size(0), w.size(1), x.size(2),
+                                  x.size(3), w.size(0) / groups, w.size(2),
+                                  stride, pad);
     const int esz = (int)x.element_size();
-    const int nkc = (kchunks + splitk - 1) / splitk;
-    int win_bytes = 0;
-    const bool resident =
-        staged && !fp8 && resident_on() && P % BP == 0 && 2 * gm.pad <= WGAP
-        && resident_plan(nkc, gm.khw * gm.khw, gm.Cin,
-                         (BP / gm.OW - 1) * gm.stride + gm.khw, gm.W, esz, 2,
-                         &win_bytes);
+    const ConvPlan pl = plan_fwd(gm, esz, fp8 != 0);
+    auto y = at::empty({gm.N, gm.G * gm.Cout, gm.OH, gm.OW}, x.options());
+    at::Tensor partial;
+    if (pl.split > 1)
+        partial = at::empty({(long)pl.split * y.numel()},
+                            x.options().dtype(at::kFloat));
+    float* pp = pl.split > 1 ? partial.data_ptr<float>() : nullptr;
+    const float* wp = w.data_ptr<float>();
+    const float* bp = bias.defined() ? bias.data_ptr<float>() : nullptr;
+    auto stream = at::hip::getCurrentHIPStream();
     DISPATCH_CONV_FT(x.scalar_type(), {
-        if (resident) {
+        const scalar_t* xp = (const scalar_t*)x.data_ptr();
+        const scalar_t* rp = residual.defined()
+                                 ? (const scalar_t*)residual.data_ptr()
+                                 : nullptr;
+        scalar_t* yp = (scalar_t*)y.data_ptr();
+        if (pl.route == RESIDENT) {
+            const int K = gm.Cin * gm.khw * gm.khw;
             const int flags =
-                ((gm.W % (16 / esz) == 0 && aligned16(x.data_ptr())) ? 1 : 0)
-                | ((K % 4 == 0 && aligned16(w.data_ptr())) ? 2 : 0);
-            hipLaunchKernelGGL((conv_fwd_resident_kernel<scalar_t>), grid,
-                               dim3(256), win_bytes + nkc * BK * 2, stream,
-                               (const scalar_t*)x.data_ptr(),
-                               w.data_ptr<float>(),
-                               bias.defined() ? bias.data_ptr<float>()
-                                              : nullptr,
-                               residual.defined()
-                                   ? (const scalar_t*)residual.data_ptr()
-                                   : nullptr,
-                               (scalar_t*)y.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk, win_bytes, flags);
-        } else if (staged_ms && !fp8) {
-            hipLaunchKernelGGL((conv_fwd_staged_ms_kernel<scalar_t, scalar_t,
-                                                          scalar_t>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)x.data_ptr(),
-                               w.data_ptr<float>(),
-                               bias.defined() ? bias.data_ptr<float>()
-                                              : nullptr,
-                               residual.defined()
-                                   ? (const scalar_t*)residual.data_ptr()
-                                   : nullptr,
-                               (scalar_t*)y.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk);
-        } else if (staged && !fp8) {
-            hipLaunchKernelGGL((conv_fwd_staged_kernel<scalar_t, scalar_t,
-                                                       scalar_t>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)x.data_ptr(),
-                               w.data_ptr<float>(),
-                               bias.defined() ? bias.data_ptr<float>()
-                                              : nullptr,
-                               residual.defined()
-                                   ? (const scalar_t*)residual.data_ptr()
-                                   : nullptr,
-                               (scalar_t*)y.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk);
-        } else if (fp8 && x.scalar_type() == at::kBFloat16)
-            hipLaunchKernelGGL((conv_fwd_kernel<scalar_t, e4m3, e4m3>), grid,
-                               dim3(256), 0, stream,
-                               (const scalar_t*)x.data_ptr(),
-                               w.data_ptr<float>(),
-                               bias.defined() ? bias.data_ptr<float>()
-                                              : nullptr,
-                               residual.defined()
-                                   ? (const scalar_t*)residual.data_ptr()
-                                   : nullptr,
-                               (scalar_t*)y.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk);
-        else
-            hipLaunchKernelGGL((conv_fwd_kernel<scalar_t, scalar_t, scalar_t>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)x.data_ptr(),
-                               w.data_ptr<float>(),
-                               bias.defined() ? bias.data_ptr<float>()
-                                              : nullptr,
-                               residual.defined()
-                                   ? (const scalar_t*)residual.data_ptr()
-                                   : nullptr,
-                               (scalar_t*)y.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk);
-        if (splitk > 1) {
+                ((gm.W % (16 / esz) == 0 && aligned16(xp)) ? 1 : 0)
+                | ((K % 4 == 0 && aligned16(wp)) ? 2 : 0);
+            hipLaunchKernelGGL(conv_fwd_resident_kernel<scalar_t>, pl.grid,
+                               dim3(256), pl.dyn_lds, stream, xp, wp, bp, rp,
+                               yp, pp, gm, pl.split, pl.tab0, flags);
+        } else {
+            hipLaunchKernelGGL(fwd_kernel<scalar_t>(pl), pl.grid, dim3(256),
+                               0, stream, xp, wp, bp, rp, yp, pp, gm,
+                               pl.split);
+        }
+        if (pl.split > 1) {
             const long total = y.numel();
-            const int blocks = (int)((total + 255) / 256);
-            hipLaunchKernelGGL(conv_out_reduce_kernel<scalar_t>, dim3(blocks),
-                               dim3(256), 0, stream,
-                               partial.data_ptr<float>(),
-                               bias.defined() ? bias.data_ptr<float>()
-                                              : nullptr,
-                               residual.defined()
-                                   ? (const scalar_t*)residual.data_ptr()
-                                   : nullptr,
-                               (scalar_t*)y.data_ptr(), total,
-                               (long)gm.OH * gm.OW, gm.G * gm.Cout, splitk);
+            hipLaunchKernelGGL(conv_out_reduce_kernel<scalar_t>,
+                               dim3((int)((total + 255) / 256)), dim3(256), 0,
+                               stream, pp, bp, rp, yp, total,
+                               (long)gm.OH * gm.OW, gm.G * gm.Cout, pl.split);
         }
     });
     return y;
@@ -2247,153 +2035,45 @@ at::Tensor conv_bwd_data(at::Tensor dy, at::Tensor w, int64_t groups,
     TORCH_CHECK(dy.is_cuda() && w.is_contiguous());
     TORCH_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
     auto dyc = dy.contiguous();
-    ConvGeom gm;
-    gm.G = (int)groups;
-    gm.N = dy.size(0);
-    gm.H = (int)H;
-    gm.W = (int)W;
-    gm.Cin = (int)w.size(1);
-    gm.Cout = (int)(w.size(0) / groups);
-    gm.khw = (int)w.size(2);
-    gm.stride = (int)stride;
-    gm.pad = (int)pad;
-    gm.OH = dy.size(2);
-    gm.OW = dy.size(3);
-    auto dx = at::empty({gm.N, gm.G * gm.Cin, gm.H, gm.W}, dy.options());
-    const int Q = gm.N * gm.H * gm.W;
-    const bool s2 = (gm.stride == 2 && gm.H % 2 == 0 && gm.W % 2 == 0);
-    // parity path: 4 classes of Q/4 pixels, ~1/4 the taps each
-    const int Jfull = gm.Cout * gm.khw * gm.khw;
-    const int J = s2 ? (Jfull + 3) / 4 : Jfull;
-    const int jchunks = (J + BK - 1) / BK;
-    const int qtile = s2 ? Q / 4 : Q;
-    const int nyp = (qtile + BP - 1) / BP;
-    const int tiles = ((gm.Cin + BM - 1) / BM) * nyp * (s2 ? 4 : 1) * gm.G;
-    int splitk = 1;
-    static const bool noskip_d = [] {
-        const char* e = std::getenv("HETEROFL_SPLIT_NOSKIP");
-        return e && e[0] == '1';
-    }();
-    if (noskip_d || J > 1024 || tiles < 512)
-        while (tiles * splitk < split_target() && splitk * 2 <= jchunks / 2)
-            splitk *= 2;
-    dim3 grid((gm.Cin + BM - 1) / BM, nyp * (s2 ? 4 : 1), gm.G * splitk);
-    auto stream = at::hip::getCurrentHIPStream();
-    at::Tensor partial;
-    if (splitk > 1)
-        partial = at::empty({(long)splitk * dx.numel()},
-                            dy.options().dtype(at::kFloat));
-    const bool stg = !s2 && gm.stride == 1
-                     && (gm.H * gm.W) % BP == 0 && BP % gm.W == 0
-                     && (gm.OW + 2 * gm.pad) <= WIN_W - 2
-                     && (BP / gm.W + gm.khw - 1) <= WIN_ROWS
-                     && (BK / (gm.khw * gm.khw) + 2) <= WIN_CH
-                     && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
-    const int HWd = gm.H * gm.W;
-    static const bool ms_on_d = [] {
-        const char* e = std::getenv("HETEROFL_CONV_MS");
-        return e && e[0] == '1';
-    }();
-    const bool stg_ms = ms_on_d && !stg && !s2 && gm.stride == 1
-                        && HWd < BP && BP % HWd == 0
-                        && (gm.OW + 2 * gm.pad) <= WIN_W - 2
-                        && (BP / HWd) * (gm.H + gm.khw - 1) <= MS_ROWS
-                        && (BK / (gm.khw * gm.khw) + 2) <= WIN_CH
-                        && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
-    // resident dy window (2*pad >= khw-1: the geometry the staged kernel's
-    // own window addressing covers)
+    const ConvGeom gm = conv_geom(groups, dy.size(0), w.size(1), H, W,
+                                  w.size(0) / groups, w.size(2), stride, pad);
+    TORCH_CHECK(dy.size(2) == gm.OH && dy.size(3) == gm.OW,
+                "dy does not match the conv geometry");
     const int esz = (int)dy.element_size();
-    const int njc = (jchunks + splitk - 1) / splitk;
-    int win_bytes = 0;
-    const bool resident =
-        stg && !fp8 && resident_on() && 2 * gm.pad <= WGAP
-        && 2 * gm.pad >= gm.khw - 1
-        && resident_plan(njc, gm.khw * gm.khw, gm.Cout,
-                         BP / gm.W + gm.khw - 1, gm.OW, esz, 6, &win_bytes);
+    const ConvPlan pl = plan_bwd_data(gm, esz, fp8 != 0);
+    auto dx = at::empty({gm.N, gm.G * gm.Cin, gm.H, gm.W}, dy.options());
+    at::Tensor partial;
+    if (pl.split > 1)
+        partial = at::empty({(long)pl.split * dx.numel()},
+                            dy.options().dtype(at::kFloat));
+    float* pp = pl.split > 1 ? partial.data_ptr<float>() : nullptr;
+    const float* wp = w.data_ptr<float>();
+    auto stream = at::hip::getCurrentHIPStream();
     DISPATCH_CONV_FT(dy.scalar_type(), {
-        const bool q = fp8 && dy.scalar_type() == at::kBFloat16;
-        if (resident) {
+        const scalar_t* dyp = (const scalar_t*)dyc.data_ptr();
+        scalar_t* dxp = (scalar_t*)dx.data_ptr();
+        if (pl.route == RESIDENT) {
             const int flags =
-                (gm.OW % (16 / esz) == 0 && aligned16(dyc.data_ptr())) ? 1 : 0;
-            hipLaunchKernelGGL((conv_bwd_data_resident_kernel<scalar_t>),
-                               grid, dim3(256), win_bytes + njc * BK * 6,
-                               stream, (const scalar_t*)dyc.data_ptr(),
-                               w.data_ptr<float>(), (scalar_t*)dx.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk, win_bytes,
-                               win_bytes + njc * BK * 4, flags);
-        } else if (stg_ms && !q) {
-            hipLaunchKernelGGL((conv_bwd_data_staged_ms_kernel<scalar_t,
-                                                               scalar_t,
-                                                               scalar_t>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               w.data_ptr<float>(), (scalar_t*)dx.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk);
-        } else if (stg && !q) {
-            hipLaunchKernelGGL((conv_bwd_data_staged_kernel<scalar_t,
-                                                            scalar_t,
-                                                            scalar_t>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               w.data_ptr<float>(), (scalar_t*)dx.data_ptr(),
-                               splitk > 1 ? partial.data_ptr<float>()
-                                          : nullptr,
-                               gm, splitk);
-        } else if (s2) {
-            if (q)
-                hipLaunchKernelGGL((conv_bwd_data_s2_kernel<scalar_t, e4m3,
-                                                            e5m2>),
-                                   grid, dim3(256), 0, stream,
-                                   (const scalar_t*)dyc.data_ptr(),
-                                   w.data_ptr<float>(),
-                                   (scalar_t*)dx.data_ptr(),
-                                   splitk > 1 ? partial.data_ptr<float>()
-                                              : nullptr,
-                                   gm, splitk, nyp);
-            else
-                hipLaunchKernelGGL((conv_bwd_data_s2_kernel<scalar_t, scalar_t,
-                                                            scalar_t>),
-                                   grid, dim3(256), 0, stream,
-                                   (const scalar_t*)dyc.data_ptr(),
-                                   w.data_ptr<float>(),
-                                   (scalar_t*)dx.data_ptr(),
-                                   splitk > 1 ? partial.data_ptr<float>()
-                                              : nullptr,
-                                   gm, splitk, nyp);
+                (gm.OW % (16 / esz) == 0 && aligned16(dyp)) ? 1 : 0;
+            hipLaunchKernelGGL(conv_bwd_data_resident_kernel<scalar_t>,
+                               pl.grid, dim3(256), pl.dyn_lds, stream, dyp,
+                               wp, dxp, pp, gm, pl.split, pl.tab0, pl.tab1,
+                               flags);
+        } else if (pl.route == GATHER_S2) {
+            hipLaunchKernelGGL(bwd_data_s2_kernel<scalar_t>(pl), pl.grid,
+                               dim3(256), 0, stream, dyp, wp, dxp, pp, gm,
+                               pl.split, pl.nyp);
         } else {
-            if (q)
-                hipLaunchKernelGGL((conv_bwd_data_kernel<scalar_t, e4m3,
-                                                         e5m2>),
-                                   grid, dim3(256), 0, stream,
-                                   (const scalar_t*)dyc.data_ptr(),
-                                   w.data_ptr<float>(),
-                                   (scalar_t*)dx.data_ptr(),
-                                   splitk > 1 ? partial.data_ptr<float>()
-                                              : nullptr,
-                                   gm, splitk);
-            else
-                hipLaunchKernelGGL((conv_bwd_data_kernel<scalar_t, scalar_t,
-                                                         scalar_t>),
-                                   grid, dim3(256), 0, stream,
-                                   (const scalar_t*)dyc.data_ptr(),
-                                   w.data_ptr<float>(),
-                                   (scalar_t*)dx.data_ptr(),
-                                   splitk > 1 ? partial.data_ptr<float>()
-                                              : nullptr,
-                                   gm, splitk);
+            hipLaunchKernelGGL(bwd_data_kernel<scalar_t>(pl), pl.grid,
+                               dim3(256), 0, stream, dyp, wp, dxp, pp, gm,
+                               pl.split);
         }
-        if (splitk > 1) {
+        if (pl.split > 1) {
             const long total = dx.numel();
-            const int blocks = (int)((total + 255) / 256);
-            hipLaunchKernelGGL(conv_out_reduce_kernel<scalar_t>, dim3(blocks),
-                               dim3(256), 0, stream,
-                               partial.data_ptr<float>(), nullptr, nullptr,
-                               (scalar_t*)dx.data_ptr(), total, 1L, 1,
-                               splitk);
+            hipLaunchKernelGGL(conv_out_reduce_kernel<scalar_t>,
+                               dim3((int)((total + 255) / 256)), dim3(256), 0,
+                               stream, pp, nullptr, nullptr, dxp, total, 1L,
+                               1, pl.split);
         }
     });
     return dx;
@@ -2403,146 +2083,43 @@ at::Tensor conv_bwd_weight(at::Tensor dy, at::Tensor x, int64_t groups,
                            int64_t stride, int64_t pad, int64_t khw,
                            int64_t fp8) {
     auto dyc = dy.contiguous();
-    ConvGeom gm;
-    gm.G = (int)groups;
-    gm.N = x.size(0);
-    gm.H = x.size(2);
-    gm.W = x.size(3);
-    gm.Cin = (int)(x.size(1) / groups);
-    gm.Cout = (int)(dy.size(1) / groups);
-    gm.khw = (int)khw;
-    gm.stride = (int)stride;
-    gm.pad = (int)pad;
-    gm.OH = dy.size(2);
-    gm.OW = dy.size(3);
-    const int K = gm.Cin * gm.khw * gm.khw;
-    const int P = gm.N * gm.OH * gm.OW;
-    const long GK = (long)gm.G * gm.Cout * K;
-    const int mk_tiles = ((gm.Cout + BM - 1) / BM) * ((K + BP - 1) / BP)
-                         * gm.G;
-    int splitp = 1;
-    // measured (bwdw2 r2): small-P shapes that already have >=512 (m,k)
-    // tiles need no split at all — L3 bwdW 89.4us (splitp 2) -> 74.5us
-    // (splitp 1) = 1.00x MIOpen; splitting only pays when tiles are scarce
-    // or P is long enough to amortize the partial reduce
-    if (P > 1024 || mk_tiles < 512)
-        while (mk_tiles * splitp < split_target() && splitp * BK * 4 < P)
-            splitp *= 2;
-    // measured NEGATIVE (bwdw_sweep r2): pushing split-P further on small-P
-    // shapes (L3: splitp 8 -> 95.6us vs 89.4us at splitp 2) trades too much
-    // partial-reduce traffic for the extra blocks; default off, kept gated
-    // for future study (HETEROFL_BWDW_SMALLP=1)
-    static const bool smallp_boost = [] {
-        const char* e = std::getenv("HETEROFL_BWDW_SMALLP");
-        return e && e[0] == '1';
-    }();
-    if (smallp_boost)
-        while (P <= 2048 && mk_tiles * splitp < 4 * split_target()
-               && splitp * BK < P)
-            splitp *= 2;
+    const ConvGeom gm = conv_geom(groups, x.size(0), x.size(1) / groups,
+                                  x.size(2), x.size(3), dy.size(1) / groups,
+                                  khw, stride, pad);
+    TORCH_CHECK(dy.size(2) == gm.OH && dy.size(3) == gm.OW,
+                "dy does not match the conv geometry");
+    const int esz = (int)x.element_size();
+    const ConvPlan pl = plan_bwd_weight(gm, esz, fp8 != 0);
+    const long GK = (long)gm.G * gm.Cout * gm.Cin * gm.khw * gm.khw;
     auto dw = at::empty({(long)gm.G * gm.Cout, gm.Cin, gm.khw, gm.khw},
                         x.options().dtype(at::kFloat));
+    // split-P partials are summed in fixed order by splitp_reduce_kernel
+    at::Tensor partials;
+    if (pl.split > 1)
+        partials = at::empty({pl.split, GK}, x.options().dtype(at::kFloat));
+    float* out = pl.split > 1 ? partials.data_ptr<float>()
+                              : dw.data_ptr<float>();
     auto stream = at::hip::getCurrentHIPStream();
-    dim3 grid((gm.Cout + BM - 1) / BM, (K + BP - 1) / BP, gm.G * splitp);
-    const bool q = fp8 && x.scalar_type() == at::kBFloat16;
-    // staged path: 3x3 kernels (a 64-wide k-tile then spans <= 9 input
-    // channels = WWIN_CH), p-steps inside one sample spanning whole rows
-    const bool stg = gm.khw == 3 && (gm.OH * gm.OW) % BK == 0
-                     && BK % gm.OW == 0
-                     && (gm.W + 2 * gm.pad) <= WIN_W - 2
-                     && ((BK / gm.OW - 1) * gm.stride + gm.khw) <= WIN_ROWS
-                     && std::getenv("HETEROFL_CONV_NO_STAGED") == nullptr;
-    // resident x window: one sample segment of the p-chunk at a time
-    const int esz = (int)x.element_size();
-    const int OHWw = gm.OH * gm.OW;
-    const int pchunk = (((P + splitp - 1) / splitp + BK - 1) / BK) * BK;
-    const long wwin = (long)std::min(gm.Cin, WWIN_CH)
-                          * ((std::min(pchunk, OHWw) / gm.OW - 1) * gm.stride
-                             + gm.khw) * (gm.W + WGAP) + WGAP;
-    const int wwin_bytes = (int)((wwin * esz + 15) / 16 * 16);
-    const bool resident = stg && !q && resident_on() && 2 * gm.pad <= WGAP
-                          && 2L * (BM + BP) * LDK * esz + wwin * esz
-                                 <= resident_lds_cap();
-    if (resident) {
-        const int flags =
-            ((gm.W % (16 / esz) == 0 && aligned16(x.data_ptr())) ? 1 : 0)
-            | (aligned16(dyc.data_ptr()) ? 2 : 0);
-        at::Tensor partials;
-        if (splitp > 1)
-            partials = at::empty({splitp, GK}, x.options().dtype(at::kFloat));
-        DISPATCH_CONV_FT(x.scalar_type(), {
-            hipLaunchKernelGGL((conv_bwd_weight_resident_kernel<scalar_t>),
-                               grid, dim3(256), wwin_bytes, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               (const scalar_t*)x.data_ptr(),
-                               splitp > 1 ? partials.data_ptr<float>()
-                                          : dw.data_ptr<float>(),
-                               gm, (int)splitp, flags);
-        });
-        if (splitp > 1) {
-            const int blocks = (int)((GK + 255) / 256);
-            hipLaunchKernelGGL(splitp_reduce_kernel, dim3(blocks), dim3(256),
-                               0, stream, partials.data_ptr<float>(),
-                               dw.data_ptr<float>(), GK, splitp);
-        }
-        return dw;
-    }
-    if (splitp == 1) {
-        DISPATCH_CONV_FT(x.scalar_type(), {
-            if (q)
-                hipLaunchKernelGGL((conv_bwd_weight_kernel<scalar_t, e5m2,
-                                                           e4m3>),
-                                   grid, dim3(256), 0, stream,
-                                   (const scalar_t*)dyc.data_ptr(),
-                                   (const scalar_t*)x.data_ptr(),
-                                   dw.data_ptr<float>(), gm, 1);
-            else if (stg)
-                hipLaunchKernelGGL((conv_bwd_weight_staged_kernel<scalar_t,
-                                                                  scalar_t,
-                                                                  scalar_t>),
-                                   grid, dim3(256), 0, stream,
-                                   (const scalar_t*)dyc.data_ptr(),
-                                   (const scalar_t*)x.data_ptr(),
-                                   dw.data_ptr<float>(), gm, 1);
-            else
-                hipLaunchKernelGGL((conv_bwd_weight_kernel<scalar_t, scalar_t,
-                                                           scalar_t>),
-                                   grid, dim3(256), 0, stream,
-                                   (const scalar_t*)dyc.data_ptr(),
-                                   (const scalar_t*)x.data_ptr(),
-                                   dw.data_ptr<float>(), gm, 1);
-        });
-        return dw;
-    }
-    auto partials = at::empty({splitp, GK}, x.options().dtype(at::kFloat));
     DISPATCH_CONV_FT(x.scalar_type(), {
-        if (q)
-            hipLaunchKernelGGL((conv_bwd_weight_kernel<scalar_t, e5m2, e4m3>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               (const scalar_t*)x.data_ptr(),
-                               partials.data_ptr<float>(), gm, splitp);
-        else if (stg)
-            hipLaunchKernelGGL((conv_bwd_weight_staged_kernel<scalar_t,
-                                                              scalar_t,
-                                                              scalar_t>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               (const scalar_t*)x.data_ptr(),
-                               partials.data_ptr<float>(), gm, splitp);
-        else
-            hipLaunchKernelGGL((conv_bwd_weight_kernel<scalar_t, scalar_t,
-                                                       scalar_t>),
-                               grid, dim3(256), 0, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               (const scalar_t*)x.data_ptr(),
-                               partials.data_ptr<float>(), gm, splitp);
+        const scalar_t* dyp = (const scalar_t*)dyc.data_ptr();
+        const scalar_t* xp = (const scalar_t*)x.data_ptr();
+        if (pl.route == RESIDENT) {
+            const int flags =
+                ((gm.W % (16 / esz) == 0 && aligned16(xp)) ? 1 : 0)
+                | (aligned16(dyp) ? 2 : 0);
+            hipLaunchKernelGGL(conv_bwd_weight_resident_kernel<scalar_t>,
+                               pl.grid, dim3(256), pl.dyn_lds, stream, dyp,
+                               xp, out, gm, pl.split, flags);
+        } else {
+            hipLaunchKernelGGL(bwd_weight_kernel<scalar_t>(pl), pl.grid,
+                               dim3(256), 0, stream, dyp, xp, out, gm,
+                               pl.split);
+        }
     });
-    const int threads = 256;
-    const int blocks = (int)((GK + threads - 1) / threads);
-    hipLaunchKernelGGL(splitp_reduce_kernel, dim3(blocks), dim3(threads), 0,
-                       stream, partials.data_ptr<float>(),
-                       dw.data_ptr<float>(), GK, splitp);
+    if (pl.split > 1)
+        hipLaunchKernelGGL(splitp_reduce_kernel,
+                           dim3((int)((GK + 255) / 256)), dim3(256), 0,
+                           stream, out, dw.data_ptr<float>(), GK, pl.split);
     return dw;
 }
 

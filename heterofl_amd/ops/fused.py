@@ -178,6 +178,18 @@ def grouped_conv(x, weight, bias, groups, stride, pad, residual=None):
     return _GroupedConv.apply(x, weight, bias, residual, groups, stride, pad)
 
 
+def conv_plan(direction, G, N, Cin, H, W, Cout, khw, stride, pad, elem_size,
+              fp8):
+    """(route, split, dyn_lds_bytes) that conv_fwd / conv_bwd_data /
+    conv_bwd_weight (direction 'fwd' / 'bwd_data' / 'bwd_weight') take for
+    this shape; the launchers' own plan functions, nothing is launched.
+    route is 'resident', 'staged', 'gather' or 'gather_s2', with '_fp8'
+    appended where the fp8 tile instantiation runs."""
+    ext = require_native()
+    return ext.conv_plan(direction, G, N, Cin, H, W, Cout, khw, stride, pad,
+                         elem_size, fp8)
+
+
 # ------------------------------------------------- large-batch inference ops
 def large_conv_supported(k, stride, pad):
     """Shapes conv_fwd_large implements: 3x3/pad 1 and 1x1/pad 0, stride 1

@@ -50,8 +50,7 @@ def miopen():
 
 tm = timeit(miopen)
 tag = os.environ.get('HETEROFL_CONV_SPLIT_TARGET', 'default')
-nostg = 'nostaged' if os.environ.get('HETEROFL_CONV_NO_STAGED') else 'staged'
-print(f'L3 bwdW [{nostg}, split_target={tag}]: native {tn:.1f}us '
+print(f'L3 bwdW [split_target={tag}]: native {tn:.1f}us '
       f'miopen {tm:.1f}us ratio {tn / tm:.2f}')
 err = (ext.conv_bwd_weight(dy, x, G, s, p, k, 0)
        - miopen().float()).abs().max().item()

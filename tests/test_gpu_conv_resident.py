@@ -1,6 +1,7 @@
 """Resident-window grouped-conv kernels (ops/csrc/conv_mfma.hip) against
 the staged kernels they replace (bit-exact, HETEROFL_CONV_RESIDENT=0) and
-against F.conv2d / autograd on fp32 copies.  Run with: pytest tests -m gpu"""
+against F.conv2d / autograd on fp32 copies, and the table of which kernel
+and split each shape takes.  Run with: pytest tests -m gpu"""
 import contextlib
 import functools
 import os
@@ -131,6 +132,111 @@ def test_resident_bwd_data(case, dname):
 def test_resident_bwd_weight(case, dname):
     G, N, Cin, H, Cout, k, s, p = CASES[case]
     check(case, dname, 'bwdW', 5e-3 * N * H)
+
+
+# ---------------------------------------------------------------- route table
+# Which kernel and split every shape takes (ops.fused.conv_plan: the
+# launchers' own plan functions, nothing launched).  Shapes: CASES above plus
+# the seven of test_gpu.py::test_mfma_conv_matches_torch.  Rows are
+# (fwd, bwd_data, bwd_weight) as (route, split) with the resident toggle on
+# and fp8 off, recorded from the host layer as it stood before the routing
+# was factored into plan functions (commit e9e3335); the A/C/E/F/H anchors
+# are the ones the CASES comments claim.
+ROUTE_SHAPES = dict(CASES, **{
+    'stem': (5, 10, 3, 32, 64, 3, 1, 1),
+    'layer1': (5, 10, 64, 32, 64, 3, 1, 1),
+    'down': (5, 10, 64, 32, 128, 3, 2, 1),
+    'short': (5, 10, 64, 32, 128, 1, 2, 0),
+    'layer4': (5, 10, 512, 4, 512, 3, 1, 1),
+    'r16': (3, 10, 4, 32, 4, 3, 1, 1),
+    'odd': (2, 7, 20, 16, 36, 3, 2, 1),
+})
+R, S, GA, G2 = 'resident', 'staged', 'gather', 'gather_s2'
+ROUTES = {
+    'A': {'bf16': ((R, 2), (R, 4), (R, 4)), 'fp32': ((R, 2), (R, 4), (R, 4))},
+    'B': {'bf16': ((R, 2), (G2, 1), (R, 4)),
+          'fp32': ((R, 2), (G2, 1), (R, 4))},
+    'C': {'bf16': ((GA, 1), (G2, 1), (GA, 4)),
+          'fp32': ((GA, 1), (G2, 1), (GA, 4))},
+    'D': {'bf16': ((R, 1), (R, 1), (R, 16)),
+          'fp32': ((R, 1), (R, 1), (R, 16))},
+    'E': {'bf16': ((R, 4), (R, 2), (R, 2)), 'fp32': ((R, 4), (R, 2), (R, 2))},
+    'F': {'bf16': ((R, 32), (R, 8), (R, 1)),
+          'fp32': ((R, 32), (R, 8), (R, 1))},
+    'G': {'bf16': ((R, 1), (R, 8), (R, 16)),
+          'fp32': ((R, 1), (R, 8), (R, 16))},
+    'H': {'bf16': ((S, 1), (S, 1), (R, 8)), 'fp32': ((S, 1), (S, 1), (S, 8))},
+    'stem': {'bf16': ((R, 1), (R, 1), (R, 128)),
+             'fp32': ((R, 1), (S, 1), (R, 128))},
+    'layer1': {'bf16': ((R, 1), (R, 1), (R, 32)),
+               'fp32': ((S, 1), (S, 1), (R, 32))},
+    'down': {'bf16': ((R, 4), (G2, 1), (R, 16)),
+             'fp32': ((S, 4), (G2, 1), (S, 16))},
+    'short': {'bf16': ((GA, 1), (G2, 1), (GA, 32)),
+              'fp32': ((GA, 1), (G2, 1), (GA, 32))},
+    'layer4': {'bf16': ((GA, 16), (GA, 16), (GA, 1)),
+               'fp32': ((GA, 16), (GA, 16), (GA, 1))},
+    'r16': {'bf16': ((R, 1), (R, 1), (R, 128)),
+            'fp32': ((R, 1), (R, 1), (R, 128))},
+    'odd': {'bf16': ((GA, 2), (G2, 1), (R, 4)),
+            'fp32': ((GA, 2), (G2, 1), (R, 4))},
+}
+# bf16 with fp8=1: every direction runs the fp8 instantiation of its gather
+# kernel, the toggle either way; bwd-data's kernel per shape (same source)
+FP8_BWD_DATA = {
+    'A': GA, 'B': G2, 'C': G2, 'D': GA, 'E': GA, 'F': GA, 'G': GA, 'H': GA,
+    'stem': GA, 'layer1': GA, 'down': G2, 'short': G2, 'layer4': GA,
+    'r16': GA, 'odd': G2}
+# fp32 with fp8=1 (no fp8 tiles for fp32): fwd drops to the plain gather
+# kernel, bwd-data to the staged kernel, bwd-weight ignores the flag
+FP32_FP8 = {
+    'A': ((GA, 2), (S, 4), (R, 4)),
+    'layer1': ((GA, 1), (S, 1), (R, 32)),
+}
+DIRECTIONS = ('fwd', 'bwd_data', 'bwd_weight')
+
+
+def plans(shape, dname, fp8):
+    from heterofl_amd.ops.fused import conv_plan
+    G, N, Cin, H, Cout, k, s, p = ROUTE_SHAPES[shape]
+    esz = {'bf16': 2, 'fp32': 4}[dname]
+    out = []
+    for d in DIRECTIONS:
+        route, split, lds = conv_plan(d, G, N, Cin, H, H, Cout, k, s, p, esz,
+                                      fp8)
+        assert (lds > 0) == (route == R), (shape, dname, d, route, lds)
+        out.append((route, split))
+    return tuple(out)
+
+
+def staged_for_resident(row):
+    return tuple((S if r == R else r, sp) for r, sp in row)
+
+
+@needs_gpu
+@pytest.mark.parametrize('shape', list(ROUTE_SHAPES))
+def test_conv_route_table(shape):
+    assert set(ROUTES) == set(ROUTE_SHAPES) == set(FP8_BWD_DATA)
+    for dname in DTYPES:
+        want = ROUTES[shape][dname]
+        with resident(True):
+            assert plans(shape, dname, 0) == want, (shape, dname)
+        # toggle off: every resident becomes staged with the same split
+        with resident(False):
+            assert plans(shape, dname, 0) == staged_for_resident(want), \
+                (shape, dname)
+    splits = [sp for _, sp in ROUTES[shape]['bf16']]
+    want8 = tuple(zip((GA + '_fp8', FP8_BWD_DATA[shape] + '_fp8',
+                       GA + '_fp8'), splits))
+    for on in (True, False):
+        with resident(on):
+            assert plans(shape, 'bf16', 1) == want8, (shape, on)
+    if shape in FP32_FP8:
+        want = FP32_FP8[shape]
+        with resident(True):
+            assert plans(shape, 'fp32', 1) == want, shape
+        with resident(False):
+            assert plans(shape, 'fp32', 1) == staged_for_resident(want), shape
 
 
 @needs_gpu
