@@ -42,6 +42,10 @@ std::tuple<std::string, int64_t, int64_t> conv_plan(
     const std::string& direction, int64_t G, int64_t N, int64_t Cin,
     int64_t H, int64_t W, int64_t Cout, int64_t khw, int64_t stride,
     int64_t pad, int64_t elem_size, int64_t fp8);
+std::string conv_plan_variant(
+    const std::string& direction, int64_t G, int64_t N, int64_t Cin,
+    int64_t H, int64_t W, int64_t Cout, int64_t khw, int64_t stride,
+    int64_t pad, int64_t elem_size, int64_t fp8);
 at::Tensor mfma_probe(at::Tensor A, at::Tensor B);
 std::vector<at::Tensor> head_fwd(at::Tensor feat, at::Tensor w, at::Tensor b,
                                  int64_t R);
@@ -127,6 +131,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv_plan", &conv_plan,
           "(route, split, dynamic LDS bytes) the conv launchers would take; "
           "launches nothing");
+    m.def("conv_plan_variant", &conv_plan_variant,
+          "name of the kernel the conv launcher would launch; launches "
+          "nothing");
     m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
     m.def("head_fwd", &head_fwd, "fused avgpool+per-client-linear forward");
     m.def("head_bwd", &head_bwd, "fused head backward");

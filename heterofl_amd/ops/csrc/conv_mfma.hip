@@ -36,8 +36,16 @@
 //             HETEROFL_CONV_RESIDENT=0 turns it off.
 //   staged    conv_*_staged_kernel: window restaged per k-step; the
 //             fallback and the bit-exact oracle of the resident kernels.
+//   tabled    conv_fwd_tabled_kernel, conv_bwd_data{,_s2}_tabled_kernel,
+//             conv_bwd_weight_tabled_kernel: any geometry; the reduction
+//             index decode and the bounds tests come from per-block tables
+//             and per-pixel tap masks built in the prologue, tiles are
+//             double-buffered.  Taken on the gather routes for bf16/fp32
+//             while the slice's table fits its capacity;
+//             HETEROFL_CONV_TABLED=0 turns it off.
 //   gather    conv_fwd_kernel, conv_bwd_data{,_s2}_kernel,
-//             conv_bwd_weight_kernel: any geometry, fp8 instantiations.
+//             conv_bwd_weight_kernel: any geometry, fp8 instantiations; the
+//             fallback and the bit-exact oracle of the tabled kernels.
 // The multi-sample staged fwd / bwd-data kernels and the opt-in switch that
 // selected them measured slower than the gather kernels (profiles/NOTES.md)
 // and were removed; commit 67e6a3a is the last that carries them.
@@ -1691,6 +1699,608 @@ conv_bwd_weight_resident_kernel(const T* __restrict__ dy,
             }
 }
 
+// --------------------------------------------------- tabled gather kernels
+// The gather kernels above decode every loaded element's reduction index
+// (k -> cin, kh, kw; j -> cout, kh, kw) and bounds-test it with four
+// compares inside the k-loop; their loop bodies are ~500-1400 instructions
+// around four MFMAs (profiles/NOTES.md, "tabled gather").  None of that
+// depends on data.  The tabled variants build, once per block:
+//   - a reduction-index table for the block's own slice: per entry the
+//     element's offset relative to the pixel base and its tap index, packed
+//     (offset << 4) | tap; tap 15 marks an entry past the slice end;
+//   - per pixel a tap-validity mask (bit tap = that tap lands inside the
+//     image), next to the pixel base;
+//   - a block-uniform flag: every tap of every pixel of the tile is valid,
+//     so interior chunks skip the mask test altogether.
+// An element is then `(mask >> tap) & 1 ? src[base + offset] : 0`.  Loads
+// stay raw T (no float round trip).  Operands, their K/J/P order, the BK
+// chunking, the split rules and the wave-to-quadrant mapping are those of
+// the gather kernels, so results are bit-identical (HETEROFL_CONV_TABLED=0
+// routes back to them for A/B).  bf16 and fp32 only; fp8 stays on the old
+// kernels, and so does any slice whose table exceeds the capacities below.
+// The reduction tables live in dynamic LDS sized by the slice (4 bytes per
+// entry fwd, 8 bwd-data), so a short slice does not pay for the capacity.
+// The flagship's largest slices: 576 entries (layer 4 with 6-10 full-width
+// clients in the group, split 8) and 1024 (the 16x16 stride-2 bwd-data,
+// unsplit from 7 clients on); its bwd-weight chunks are at most 160 pixels.
+constexpr int TAB_CAP = 1024;       // k / j entries per slice (32 BK-chunks)
+constexpr int PIX_TAB_CAP = 256;    // bwd-weight: pixels per p-chunk
+constexpr int TAP_NONE = 15;        // table entry past the slice end
+
+// one gathered raw element: entry = (offset << 4) | tap, offset signed
+template <typename R>
+__device__ __forceinline__ R gather_elem(const R* src, long base, int entry,
+                                         unsigned mask) {
+    return ((mask >> (entry & 15)) & 1u) ? src[base + (entry >> 4)] : (R)0;
+}
+
+// flags: bit 1 = weight rows take float4 loads (K % 4 == 0, base aligned).
+template <typename T>
+__global__ void __launch_bounds__(256)
+conv_fwd_tabled_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                       const float* __restrict__ bias,
+                       const T* __restrict__ residual, T* __restrict__ y,
+                       float* __restrict__ partial, ConvGeom gm, int splitk,
+                       int flags) {
+    typedef typename RawOf<T>::type R;
+    __shared__ T a_lds[2][BM][LDK];
+    __shared__ T b_lds[2][BP][LDK];
+    extern __shared__ __align__(16) unsigned char dyn_lds[];
+    int* ktab = (int*)dyn_lds;          // nkc * BK entries
+    __shared__ long t_ybase[BP];
+    const TileCoord tc = tile_coord(gm.G);
+    const int g = tc.g, sp = tc.sp;
+    const int m0 = tc.row0, p0 = tc.col0;
+    const int kk2 = gm.khw * gm.khw;
+    const int K = gm.Cin * kk2;
+    const int M = gm.Cout;
+    const int OHW = gm.OH * gm.OW;
+    const int P = gm.N * OHW;
+    const int HW = gm.H * gm.W;
+    const int tid = tc.tid, l = tc.l, wm = tc.wm, wp = tc.wp;
+    const int nkc = ((K + BK - 1) / BK + splitk - 1) / splitk;
+    const int ks = sp * nkc * BK;
+    const int ke = min(K, ks + nkc * BK);
+    const int mm_a = tid >> 2, kkb = (tid & 3) * 8;
+    const int pp_b = tid >> 2;
+
+    // prologue: this thread's pixel (base + tap mask), the k table
+    long xbase = 0;
+    unsigned mask = 0;
+    {
+        const int p = p0 + pp_b;
+        if (p < P) {
+            const int n = p / OHW, hw = p - n * OHW;
+            const int oh = hw / gm.OW, ow = hw - oh * gm.OW;
+            const int ihb = oh * gm.stride - gm.pad;
+            const int iwb = ow * gm.stride - gm.pad;
+            xbase = ((long)n * gm.G * gm.Cin + (long)g * gm.Cin) * HW
+                    + ihb * gm.W + iwb;
+            for (int kh = 0; kh < gm.khw; ++kh)
+                for (int kw = 0; kw < gm.khw; ++kw) {
+                    const int ih = ihb + kh, iw = iwb + kw;
+                    if (ih >= 0 && ih < gm.H && iw >= 0 && iw < gm.W)
+                        mask |= 1u << (kh * gm.khw + kw);
+                }
+            if ((tid & 3) == 0)
+                t_ybase[pp_b] = ((long)n * gm.G * gm.Cout
+                                 + (long)g * gm.Cout) * OHW + hw;
+        } else if ((tid & 3) == 0) {
+            t_ybase[pp_b] = -1;
+        }
+    }
+    for (int i = tid; i < nkc * BK; i += 256) {
+        const int k = ks + i;
+        int e = TAP_NONE;
+        if (k < ke) {
+            const int cin = k / kk2, r = k - cin * kk2;
+            const int kh = r / gm.khw, kw = r - kh * gm.khw;
+            e = ((cin * HW + kh * gm.W + kw) << 4) | r;
+        }
+        ktab[i] = e;
+    }
+    // (also the barrier that publishes ktab and t_ybase)
+    const bool interior = __syncthreads_and(mask == (1u << kk2) - 1u);
+    const bool m_full = (m0 + BM <= M);
+    const float* wrow0 = w + (long)(g * gm.Cout + m0 + mm_a) * K + kkb;
+    const R* xr = (const R*)x;
+
+    f32x4 acc[2][2] = {};
+    float va[8];
+    R vb[8];
+    auto load_regs = [&](int k0) {
+        const float* wrow = wrow0 + k0;
+        const bool full = (k0 + BK <= ke);           // block-uniform
+        if ((flags & 2) && m_full && full) {
+            const f32x4 lo = *(const f32x4*)wrow;
+            const f32x4 hi = *(const f32x4*)(wrow + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                va[j] = lo[j];
+                va[4 + j] = hi[j];
+            }
+        } else {
+            const bool mok = (m0 + mm_a < M);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                va[j] = (mok && k0 + kkb + j < ke) ? wrow[j] : 0.f;
+        }
+        const int* te = ktab + (k0 - ks) + kkb;
+        const u32x4 lo = *(const u32x4*)te;
+        const u32x4 hi = *(const u32x4*)(te + 4);
+        if (interior && full) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                vb[j] = xr[xbase + ((int)lo[j] >> 4)];
+                vb[4 + j] = xr[xbase + ((int)hi[j] >> 4)];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                vb[j] = gather_elem<R>(xr, xbase, (int)lo[j], mask);
+                vb[4 + j] = gather_elem<R>(xr, xbase, (int)hi[j], mask);
+            }
+        }
+    };
+    // double-buffered k-loop: one barrier per k-step, tile t+1's loads in
+    // flight across tile t's MFMA phase (as conv_fwd_kernel)
+    if (ks < ke) {
+        load_regs(ks);
+        st8_lds(&a_lds[0][mm_a][kkb], va);
+        st8_raw((R*)&b_lds[0][pp_b][kkb], vb);
+        if (ks + BK < ke) load_regs(ks + BK);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int k0 = ks; k0 < ke; k0 += BK) {
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+            for (int fp = 0; fp < 2; ++fp)
+                acc[fm][fp] = mfma_tile<T>(
+                    &a_lds[cur][wm + fm * 16 + (l & 15)][0],
+                    &b_lds[cur][wp + fp * 16 + (l & 15)][0], acc[fm][fp]);
+        if (k0 + BK < ke) {
+            st8_lds(&a_lds[cur ^ 1][mm_a][kkb], va);
+            st8_raw((R*)&b_lds[cur ^ 1][pp_b][kkb], vb);
+            if (k0 + 2 * BK < ke) load_regs(k0 + 2 * BK);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const long slab = (long)sp * gm.N * gm.G * gm.Cout * OHW;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fp = 0; fp < 2; ++fp) {
+            const int pp = wp + fp * 16 + (l & 15);
+            const long yb = t_ybase[pp];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
+                if (m < M && yb >= 0)
+                    fwd_store(acc[fm][fp][r], yb + (long)m * OHW,
+                              g * gm.Cout + m, bias, residual, y, partial,
+                              slab, splitk);
+            }
+        }
+}
+
+// bwd-data, both gather routes.  S2 = the parity-class tiling of
+// conv_bwd_data_s2_kernel (table built from the class's compressed tap
+// list, tap index = position in that list, at most 4); otherwise the
+// any-geometry kernel, stride 1 or 2.  For stride 2 there a pixel's live
+// taps are those of its own parity, and for a live tap
+// oh = (ih + pad - kh) / 2 = (ih + pad) / 2 - (kh >> 1), so the per-tap
+// part still separates from the pixel base; the parity test lives in the
+// pixel's mask.  jtab: (dy offset << 4) | tap, offset signed; wtab: the
+// strided weight offset cout*K + tap (as the resident kernel's woff).
+template <typename T, bool S2>
+__device__ __forceinline__ void
+conv_bwd_data_tabled_body(const T* __restrict__ dy,
+                          const float* __restrict__ w, T* __restrict__ dx,
+                          float* __restrict__ partial, const ConvGeom& gm,
+                          int splitk, int nyp) {
+    typedef typename RawOf<T>::type R;
+    __shared__ T a_lds[2][BM][LDK];
+    __shared__ T b_lds[2][BP][LDK];
+    extern __shared__ __align__(16) unsigned char dyn_lds[];
+    __shared__ long t_xbase[BP];
+    const int g = blockIdx.z % gm.G;
+    const int sp = blockIdx.z / gm.G;
+    const int c0 = blockIdx.x * BM;
+    const int cls = S2 ? blockIdx.y / nyp : 0;
+    const int q0 = (blockIdx.y - cls * nyp) * BP;
+    const int ph = cls >> 1, pw = cls & 1;
+    const int kk2 = gm.khw * gm.khw;
+    const int K = gm.Cin * kk2;
+    const int HW = gm.H * gm.W;
+    const int OHW = gm.OH * gm.OW;
+    const int tid = threadIdx.x;
+    const int l = tid & (WAVE - 1);
+    const int wave = tid / WAVE;
+    const int wm = (wave >> 1) * 32;
+    const int wp = (wave & 1) * 32;
+    const int cc_a = tid >> 2, jjb = (tid & 3) * 8;
+    // the tap list: S2 = taps of this parity class, else all of them
+    int nkh = gm.khw, nkw = gm.khw;
+    if (S2) {
+        nkh = nkw = 0;
+        for (int k = 0; k < gm.khw; ++k) {
+            nkh += ((ph + gm.pad - k) & 1) == 0;
+            nkw += ((pw + gm.pad - k) & 1) == 0;
+        }
+    }
+    const int tap2 = nkh * nkw;
+    const int J = gm.Cout * tap2;
+    const int njc = ((J + BK - 1) / BK + splitk - 1) / splitk;
+    const int js = sp * njc * BK;
+    const int je = min(J, js + njc * BK);
+    int* jtab = (int*)dyn_lds;          // njc * BK entries each
+    int* wtab = jtab + njc * BK;
+
+    // prologue: this thread's pixel (base + tap mask), the j tables
+    long dybase = 0;
+    unsigned mask = 0;
+    if (S2) {
+        const int H2 = gm.H >> 1, W2 = gm.W >> 1;
+        const int HW2 = H2 * W2;
+        const int q = q0 + cc_a;
+        if (q < gm.N * HW2) {
+            const int n = q / HW2, hw2 = q - n * HW2;
+            const int ih2 = hw2 / W2, iw2 = hw2 - ih2 * W2;
+            dybase = ((long)n * gm.G * gm.Cout + (long)g * gm.Cout) * OHW
+                     + ih2 * gm.OW + iw2;
+            int a = 0;
+            for (int kh = 0; kh < gm.khw; ++kh) {
+                if ((ph + gm.pad - kh) & 1) continue;
+                const int oh = ih2 + ((ph + gm.pad - kh) >> 1);
+                int b = 0;
+                for (int kw = 0; kw < gm.khw; ++kw) {
+                    if ((pw + gm.pad - kw) & 1) continue;
+                    const int ow = iw2 + ((pw + gm.pad - kw) >> 1);
+                    if (oh >= 0 && oh < gm.OH && ow >= 0 && ow < gm.OW)
+                        mask |= 1u << (a * nkw + b);
+                    ++b;
+                }
+                ++a;
+            }
+            if ((tid & 3) == 0)
+                t_xbase[cc_a] = ((long)n * gm.G * gm.Cin + (long)g * gm.Cin)
+                                    * HW
+                                + (2 * ih2 + ph) * gm.W + (2 * iw2 + pw);
+        } else if ((tid & 3) == 0) {
+            t_xbase[cc_a] = -1;
+        }
+    } else {
+        const int q = q0 + cc_a;
+        if (q < gm.N * HW) {
+            const int n = q / HW, hw = q - n * HW;
+            const int ih = hw / gm.W, iw = hw - ih * gm.W;
+            const int sh = gm.stride - 1;           // stride is 1 or 2
+            const int ohp = ih + gm.pad, owp = iw + gm.pad;
+            dybase = ((long)n * gm.G * gm.Cout + (long)g * gm.Cout) * OHW
+                     + (ohp >> sh) * gm.OW + (owp >> sh);
+            for (int kh = 0; kh < gm.khw; ++kh)
+                for (int kw = 0; kw < gm.khw; ++kw) {
+                    const int ohs = ohp - kh, ows = owp - kw;
+                    if (ohs < 0 || ows < 0) continue;
+                    if (((ohs | ows) & sh) != 0) continue;   // parity
+                    if ((ohs >> sh) < gm.OH && (ows >> sh) < gm.OW)
+                        mask |= 1u << (kh * gm.khw + kw);
+                }
+            if ((tid & 3) == 0)
+                t_xbase[cc_a] = ((long)n * gm.G * gm.Cin + (long)g * gm.Cin)
+                                    * HW + hw;
+        } else if ((tid & 3) == 0) {
+            t_xbase[cc_a] = -1;
+        }
+    }
+    for (int i = tid; i < njc * BK; i += 256) {
+        const int j = js + i;
+        int e = TAP_NONE, wo = 0;
+        if (j < je) {
+            const int cout = j / tap2, rr = j - cout * tap2;
+            if (S2) {
+                // rr-th live (kh, kw) of the class, row-major
+                const int a = rr / nkw, b = rr - a * nkw;
+                int kh = 0, kw = 0;
+                for (int k = 0, s = -1; k < gm.khw; ++k)
+                    if (((ph + gm.pad - k) & 1) == 0 && ++s == a) kh = k;
+                for (int k = 0, s = -1; k < gm.khw; ++k)
+                    if (((pw + gm.pad - k) & 1) == 0 && ++s == b) kw = k;
+                e = (cout * OHW + ((ph + gm.pad - kh) >> 1) * gm.OW
+                     + ((pw + gm.pad - kw) >> 1)) * 16 + rr;
+                wo = cout * K + kh * gm.khw + kw;
+            } else {
+                const int kh = rr / gm.khw, kw = rr - kh * gm.khw;
+                const int sh = gm.stride - 1;
+                e = (cout * OHW - (kh >> sh) * gm.OW - (kw >> sh)) * 16 + rr;
+                wo = cout * K + rr;
+            }
+        }
+        jtab[i] = e;
+        wtab[i] = wo;
+    }
+    const bool interior = __syncthreads_and(mask == (1u << tap2) - 1u);
+    const bool c_ok = (c0 + cc_a < gm.Cin);
+    const float* wbase = w + (long)g * gm.Cout * K + (long)(c0 + cc_a) * kk2;
+    const R* dyr = (const R*)dy;
+
+    f32x4 acc[2][2] = {};
+    float va[8];
+    R vb[8];
+    auto load_regs = [&](int j0) {
+        const int* wo = wtab + (j0 - js) + jjb;
+        const u32x4 wlo = *(const u32x4*)wo;
+        const u32x4 whi = *(const u32x4*)(wo + 4);
+        const int* te = jtab + (j0 - js) + jjb;
+        const u32x4 lo = *(const u32x4*)te;
+        const u32x4 hi = *(const u32x4*)(te + 4);
+        const bool full = (j0 + BK <= je);           // block-uniform
+        if (full) {
+#pragma unroll
+            for (int j8 = 0; j8 < 4; ++j8) {
+                va[j8] = c_ok ? wbase[wlo[j8]] : 0.f;
+                va[4 + j8] = c_ok ? wbase[whi[j8]] : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int j8 = 0; j8 < 4; ++j8) {
+                va[j8] = (c_ok && j0 + jjb + j8 < je) ? wbase[wlo[j8]] : 0.f;
+                va[4 + j8] = (c_ok && j0 + jjb + 4 + j8 < je)
+                                 ? wbase[whi[j8]] : 0.f;
+            }
+        }
+        if (interior && full) {
+#pragma unroll
+            for (int j8 = 0; j8 < 4; ++j8) {
+                vb[j8] = dyr[dybase + ((int)lo[j8] >> 4)];
+                vb[4 + j8] = dyr[dybase + ((int)hi[j8] >> 4)];
+            }
+        } else {
+#pragma unroll
+            for (int j8 = 0; j8 < 4; ++j8) {
+                vb[j8] = gather_elem<R>(dyr, dybase, (int)lo[j8], mask);
+                vb[4 + j8] = gather_elem<R>(dyr, dybase, (int)hi[j8], mask);
+            }
+        }
+    };
+    if (js < je) {
+        load_regs(js);
+        st8_lds(&a_lds[0][cc_a][jjb], va);
+        st8_raw((R*)&b_lds[0][cc_a][jjb], vb);
+        if (js + BK < je) load_regs(js + BK);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int j0 = js; j0 < je; j0 += BK) {
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+            for (int fp = 0; fp < 2; ++fp)
+                acc[fm][fp] = mfma_tile<T>(
+                    &a_lds[cur][wm + fm * 16 + (l & 15)][0],
+                    &b_lds[cur][wp + fp * 16 + (l & 15)][0], acc[fm][fp]);
+        if (j0 + BK < je) {
+            st8_lds(&a_lds[cur ^ 1][cc_a][jjb], va);
+            st8_raw((R*)&b_lds[cur ^ 1][cc_a][jjb], vb);
+            if (j0 + 2 * BK < je) load_regs(j0 + 2 * BK);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const long slab = (long)sp * gm.N * gm.G * gm.Cin * HW;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fp = 0; fp < 2; ++fp) {
+            const int qq = wp + fp * 16 + (l & 15);
+            const long xb = t_xbase[qq];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = c0 + wm + fm * 16 + (l >> 4) * 4 + r;
+                if (c < gm.Cin && xb >= 0) {
+                    if (splitk == 1)
+                        st_f32(dx + xb + (long)c * HW, acc[fm][fp][r]);
+                    else
+                        partial[slab + xb + (long)c * HW] = acc[fm][fp][r];
+                }
+            }
+        }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+conv_bwd_data_tabled_kernel(const T* __restrict__ dy,
+                            const float* __restrict__ w, T* __restrict__ dx,
+                            float* __restrict__ partial, ConvGeom gm,
+                            int splitk) {
+    conv_bwd_data_tabled_body<T, false>(dy, w, dx, partial, gm, splitk, 1);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+conv_bwd_data_s2_tabled_kernel(const T* __restrict__ dy,
+                               const float* __restrict__ w,
+                               T* __restrict__ dx, float* __restrict__ partial,
+                               ConvGeom gm, int splitk, int nyp) {
+    conv_bwd_data_tabled_body<T, true>(dy, w, dx, partial, gm, splitk, nyp);
+}
+
+// bwd-weight: the pixel table (x base, dy offset, tap mask) covers the
+// block's whole p-chunk and is built once; a thread's k is fixed, so its
+// offset cin*HW + kh*W + kw and its tap bit are registers.  Tiles are
+// double-buffered: one barrier per p-step (the gather kernel crosses four).
+// flags: bit 1 = a thread's 8 dy pixels are one aligned 16/32-byte load
+// (OHW % 8 == 0, p-chunk % 8 == 0, base aligned: every 8-group then lies in
+// one sample and is wholly inside or wholly outside the chunk).
+template <typename T>
+__global__ void __launch_bounds__(256)
+conv_bwd_weight_tabled_kernel(const T* __restrict__ dy,
+                              const T* __restrict__ x,
+                              float* __restrict__ out, ConvGeom gm,
+                              int splitp, int flags) {
+    typedef typename RawOf<T>::type R;
+    __shared__ T a_lds[2][BM][LDK];
+    __shared__ T b_lds[2][BP][LDK];
+    __shared__ __align__(16) int t_xb[PIX_TAB_CAP + BK];
+    __shared__ __align__(16) int t_dyb[PIX_TAB_CAP + BK];
+    __shared__ __align__(16) unsigned short t_mask[PIX_TAB_CAP + BK];
+    const int g = blockIdx.z % gm.G;
+    const int sp = blockIdx.z / gm.G;
+    const int m0 = blockIdx.x * BM;
+    const int k0 = blockIdx.y * BP;
+    const int kk2 = gm.khw * gm.khw;
+    const int K = gm.Cin * kk2;
+    const int M = gm.Cout;
+    const int OHW = gm.OH * gm.OW;
+    const int P = gm.N * OHW;
+    const int HW = gm.H * gm.W;
+    const int pchunk = (P + splitp - 1) / splitp;
+    const int pstart = sp * pchunk;
+    const int pend = min(P, pstart + pchunk);
+    const int npx = max(pend - pstart, 0);
+    const int nst = (npx + BK - 1) / BK;
+    const int tid = threadIdx.x;
+    const int l = tid & (WAVE - 1);
+    const int wave = tid / WAVE;
+    const int wm = (wave >> 1) * 32;
+    const int wp = (wave & 1) * 32;
+
+    // prologue: pixel table of the chunk, padded to whole p-steps
+    unsigned full_px = 1;
+    for (int i = tid; i < nst * BK; i += 256) {
+        const int p = pstart + i;
+        int xb = 0, db = -1;
+        unsigned mk = 0;
+        if (p < pend) {
+            const int n = p / OHW, hw = p - n * OHW;
+            const int oh = hw / gm.OW, ow = hw - oh * gm.OW;
+            const int ihb = oh * gm.stride - gm.pad;
+            const int iwb = ow * gm.stride - gm.pad;
+            xb = (n * gm.G * gm.Cin + g * gm.Cin) * HW + ihb * gm.W + iwb;
+            db = (n * gm.G * gm.Cout + g * gm.Cout) * OHW + hw;
+            for (int kh = 0; kh < gm.khw; ++kh)
+                for (int kw = 0; kw < gm.khw; ++kw) {
+                    const int ih = ihb + kh, iw = iwb + kw;
+                    if (ih >= 0 && ih < gm.H && iw >= 0 && iw < gm.W)
+                        mk |= 1u << (kh * gm.khw + kw);
+                }
+        }
+        t_xb[i] = xb;
+        t_dyb[i] = db;
+        t_mask[i] = (unsigned short)mk;
+        if (p < pend) full_px &= (mk == (1u << kk2) - 1u);
+    }
+    // every pixel of the chunk takes every tap and the k-tile is whole:
+    // whole p-steps skip the mask test
+    const bool interior = __syncthreads_and(full_px) && (k0 + BP <= K);
+
+    // per-thread ownership: row mm (A: dy row m, B: k), 8 consecutive pixels
+    const int mm = (tid >> 2) & 63, ppb = (tid & 3) * 8;
+    const bool m_ok = (m0 + mm < M);
+    const int k_b = k0 + mm;
+    const bool k_ok = (k_b < K);
+    int koff = 0;
+    unsigned kbit = 0;
+    if (k_ok) {
+        const int cin = k_b / kk2, r = k_b - cin * kk2;
+        const int kh = r / gm.khw, kw = r - kh * gm.khw;
+        koff = cin * HW + kh * gm.W + kw;
+        kbit = 1u << r;
+    }
+    const R* dyr = (const R*)dy + (long)(m0 + mm) * OHW;
+    const R* xr = (const R*)x + koff;
+    const bool dvec = (flags & 2) != 0;
+
+    f32x4 acc[2][2] = {};
+    Pack8<R> ra;
+    R vb[8];
+    auto load_regs = [&](int t) {
+        const int i0 = t * BK + ppb;
+        const u32x4 xlo = *(const u32x4*)(t_xb + i0);
+        const u32x4 xhi = *(const u32x4*)(t_xb + i0 + 4);
+        if (dvec) {
+            ra = Pack8<R>{};
+            if (m_ok && i0 < npx)
+                ra = ld8_pack<R>(dyr + t_dyb[i0], true);
+        } else {
+            const u32x4 dlo = *(const u32x4*)(t_dyb + i0);
+            const u32x4 dhi = *(const u32x4*)(t_dyb + i0 + 4);
+            R va[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                va[j] = (m_ok && (int)dlo[j] >= 0) ? dyr[(int)dlo[j]] : (R)0;
+                va[4 + j] = (m_ok && (int)dhi[j] >= 0) ? dyr[(int)dhi[j]]
+                                                       : (R)0;
+            }
+            if constexpr (sizeof(R) == 2) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    ra.v[0][j] = (unsigned)va[2 * j]
+                                 | ((unsigned)va[2 * j + 1] << 16);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    ra.v[j >> 2][j & 3] = __float_as_uint(va[j]);
+            }
+        }
+        if (interior && (t + 1) * BK <= npx) {        // block-uniform
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                vb[j] = xr[(int)xlo[j]];
+                vb[4 + j] = xr[(int)xhi[j]];
+            }
+        } else {
+            const u32x4 mv = *(const u32x4*)(t_mask + i0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const unsigned mk = (mv[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+                const int xb = (int)(j < 4 ? xlo[j & 3] : xhi[j & 3]);
+                vb[j] = (mk & kbit) ? xr[xb] : (R)0;
+            }
+        }
+    };
+    if (nst > 0) {
+        load_regs(0);
+        st8_pack((R*)&a_lds[0][mm][ppb], ra);
+        st8_raw((R*)&b_lds[0][mm][ppb], vb);
+        if (nst > 1) load_regs(1);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int t = 0; t < nst; ++t) {
+#pragma unroll
+        for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+            for (int fp = 0; fp < 2; ++fp)
+                acc[fm][fp] = mfma_tile<T>(
+                    &a_lds[cur][wm + fm * 16 + (l & 15)][0],
+                    &b_lds[cur][wp + fp * 16 + (l & 15)][0], acc[fm][fp]);
+        if (t + 1 < nst) {
+            st8_pack((R*)&a_lds[cur ^ 1][mm][ppb], ra);
+            st8_raw((R*)&b_lds[cur ^ 1][mm][ppb], vb);
+            if (t + 2 < nst) load_regs(t + 2);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const long GK = (long)gm.G * gm.Cout * K;
+    float* slab = out + (long)sp * GK;
+#pragma unroll
+    for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fp = 0; fp < 2; ++fp)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + fm * 16 + (l >> 4) * 4 + r;
+                const int k = k0 + wp + fp * 16 + (l & 15);
+                if (m < M && k < K)
+                    slab[(long)(g * gm.Cout + m) * K + k] = acc[fm][fp][r];
+            }
+}
+
 // ------------------------------------------------------------ host layer
 // Deciding is separate from launching.  plan_fwd / plan_bwd_data /
 // plan_bwd_weight are pure functions of (geometry, element size, fp8 flag)
@@ -1737,6 +2347,17 @@ static int resident_lds_cap() {
     }();
     return c;
 }
+// tabled gather routing.  HETEROFL_CONV_TABLED=0 (read on every call)
+// routes the gather routes back to the untabled kernels.  A slice is tabled
+// only while its table fits the kernel's capacity (TAB_CAP
+// reduction entries per slice, PIX_TAB_CAP pixels per p-chunk),
+// the tap index fits 4 bits with 15 spare (khw <= 3), and the packed
+// offsets fit an int; anything else, and every fp8 launch, takes the
+// untabled kernel.
+static bool tabled_on() {
+    const char* e = std::getenv("HETEROFL_CONV_TABLED");
+    return !(e && e[0] == '0');
+}
 static bool aligned16(const void* p) {
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
@@ -1782,6 +2403,8 @@ enum Route { GATHER, GATHER_S2, STAGED, RESIDENT };
 struct ConvPlan {
     Route route;
     bool fp8;       // gather kernels only: the e4m3/e5m2 tile instantiation
+    bool tabled;    // gather routes only: the tabled kernel of the route
+    int tab_lds;    // tabled fwd / bwd-data launch: dynamic LDS of its tables
     int split;      // split-K (fwd, bwd-data) or split-P (bwd-weight)
     dim3 grid;
     int dyn_lds;    // resident launch: dynamic LDS bytes
@@ -1837,6 +2460,11 @@ static ConvPlan plan_fwd(const ConvGeom& gm, int esz, bool fp8) {
     } else {
         pl.route = GATHER;
         pl.fp8 = fp8 && esz == 2;
+        // offsets cin*HW + kh*W + kw are packed above a 4-bit tap index
+        pl.tabled = !fp8 && tabled_on() && gm.khw <= 3
+                    && nkc * BK <= TAB_CAP
+                    && (long)gm.Cin * gm.H * gm.W < (1L << 27);
+        pl.tab_lds = nkc * BK * 4;
     }
     return pl;
 }
@@ -1877,6 +2505,15 @@ static ConvPlan plan_bwd_data(const ConvGeom& gm, int esz, bool fp8) {
     } else {
         pl.route = s2 ? GATHER_S2 : GATHER;
         pl.fp8 = q;
+        // the kernel's own slice: a parity class carries up to
+        // ceil(khw/2)^2 taps per output channel
+        const int t1 = s2 ? (gm.khw + 1) / 2 : gm.khw;
+        const int nj = cdiv(cdiv(gm.Cout * t1 * t1, BK), pl.split);
+        pl.tabled = !fp8 && tabled_on() && gm.khw <= 3
+                    && nj * BK <= TAB_CAP
+                    && (long)gm.Cout * gm.OH * gm.OW < (1L << 26)
+                    && (long)gm.Cout * gm.Cin * tap2 < (1L << 31);
+        pl.tab_lds = nj * BK * 8;
     }
     return pl;
 }
@@ -1907,6 +2544,11 @@ static ConvPlan plan_bwd_weight(const ConvGeom& gm, int esz, bool fp8) {
     if (!staged) {
         pl.route = GATHER;
         pl.fp8 = q;
+        // int pixel bases: both tensors index below 2^31
+        pl.tabled = !fp8 && tabled_on() && gm.khw <= 3
+                    && cdiv(P, pl.split) <= PIX_TAB_CAP
+                    && (long)gm.N * gm.G * gm.Cin * gm.H * gm.W < (1L << 31)
+                    && (long)gm.N * gm.G * gm.Cout * OHW < (1L << 31);
         return pl;
     }
     // resident x window: one sample segment of the p-chunk at a time
@@ -1943,6 +2585,36 @@ std::tuple<std::string, int64_t, int64_t> conv_plan(
                                         "resident"};
     return {std::string(names[pl.route]) + (pl.fp8 ? "_fp8" : ""), pl.split,
             pl.dyn_lds};
+}
+
+// Name of the kernel the launcher of `direction` would launch for this
+// shape (template arguments left out; "<fp8>" marks the fp8 tile
+// instantiation).  conv_plan()'s route string does not tell the tabled
+// gather kernels from the untabled ones; this does.
+std::string conv_plan_variant(
+        const std::string& direction, int64_t G, int64_t N, int64_t Cin,
+        int64_t H, int64_t W, int64_t Cout, int64_t khw, int64_t stride,
+        int64_t pad, int64_t elem_size, int64_t fp8) {
+    TORCH_CHECK(elem_size == 2 || elem_size == 4, "elem_size must be 2 or 4");
+    const ConvGeom gm = conv_geom(G, N, Cin, H, W, Cout, khw, stride, pad);
+    ConvPlan pl;
+    std::string stem;
+    if (direction == "fwd") {
+        pl = plan_fwd(gm, (int)elem_size, fp8 != 0);
+        stem = "conv_fwd";
+    } else if (direction == "bwd_data") {
+        pl = plan_bwd_data(gm, (int)elem_size, fp8 != 0);
+        stem = pl.route == GATHER_S2 ? "conv_bwd_data_s2" : "conv_bwd_data";
+    } else if (direction == "bwd_weight") {
+        pl = plan_bwd_weight(gm, (int)elem_size, fp8 != 0);
+        stem = "conv_bwd_weight";
+    } else {
+        TORCH_CHECK(false, "direction must be fwd, bwd_data or bwd_weight");
+    }
+    if (pl.route == RESIDENT) return stem + "_resident_kernel";
+    if (pl.route == STAGED) return stem + "_staged_kernel";
+    if (pl.tabled) return stem + "_tabled_kernel";
+    return stem + (pl.fp8 ? "_kernel<fp8>" : "_kernel");
 }
 
 #define DISPATCH_CONV_FT(t, ...)                                              \
@@ -2013,6 +2685,12 @@ at::Tensor conv_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
             hipLaunchKernelGGL(conv_fwd_resident_kernel<scalar_t>, pl.grid,
                                dim3(256), pl.dyn_lds, stream, xp, wp, bp, rp,
                                yp, pp, gm, pl.split, pl.tab0, flags);
+        } else if (pl.tabled) {
+            const int K = gm.Cin * gm.khw * gm.khw;
+            const int flags = (K % 4 == 0 && aligned16(wp)) ? 2 : 0;
+            hipLaunchKernelGGL(conv_fwd_tabled_kernel<scalar_t>, pl.grid,
+                               dim3(256), pl.tab_lds, stream, xp, wp, bp, rp, yp, pp,
+                               gm, pl.split, flags);
         } else {
             hipLaunchKernelGGL(fwd_kernel<scalar_t>(pl), pl.grid, dim3(256),
                                0, stream, xp, wp, bp, rp, yp, pp, gm,
@@ -2059,6 +2737,14 @@ at::Tensor conv_bwd_data(at::Tensor dy, at::Tensor w, int64_t groups,
                                pl.grid, dim3(256), pl.dyn_lds, stream, dyp,
                                wp, dxp, pp, gm, pl.split, pl.tab0, pl.tab1,
                                flags);
+        } else if (pl.tabled && pl.route == GATHER_S2) {
+            hipLaunchKernelGGL(conv_bwd_data_s2_tabled_kernel<scalar_t>,
+                               pl.grid, dim3(256), pl.tab_lds, stream, dyp, wp, dxp,
+                               pp, gm, pl.split, pl.nyp);
+        } else if (pl.tabled) {
+            hipLaunchKernelGGL(conv_bwd_data_tabled_kernel<scalar_t>,
+                               pl.grid, dim3(256), pl.tab_lds, stream, dyp, wp, dxp,
+                               pp, gm, pl.split);
         } else if (pl.route == GATHER_S2) {
             hipLaunchKernelGGL(bwd_data_s2_kernel<scalar_t>(pl), pl.grid,
                                dim3(256), 0, stream, dyp, wp, dxp, pp, gm,
@@ -2110,6 +2796,14 @@ at::Tensor conv_bwd_weight(at::Tensor dy, at::Tensor x, int64_t groups,
             hipLaunchKernelGGL(conv_bwd_weight_resident_kernel<scalar_t>,
                                pl.grid, dim3(256), pl.dyn_lds, stream, dyp,
                                xp, out, gm, pl.split, flags);
+        } else if (pl.tabled) {
+            const int OHW = gm.OH * gm.OW;
+            const int pchunk = cdiv(gm.N * OHW, pl.split);
+            const int flags = (OHW % 8 == 0 && pchunk % 8 == 0
+                               && aligned16(dyp)) ? 2 : 0;
+            hipLaunchKernelGGL(conv_bwd_weight_tabled_kernel<scalar_t>,
+                               pl.grid, dim3(256), 0, stream, dyp, xp, out,
+                               gm, pl.split, flags);
         } else {
             hipLaunchKernelGGL(bwd_weight_kernel<scalar_t>(pl), pl.grid,
                                dim3(256), 0, stream, dyp, xp, out, gm,

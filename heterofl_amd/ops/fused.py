@@ -190,6 +190,18 @@ def conv_plan(direction, G, N, Cin, H, W, Cout, khw, stride, pad, elem_size,
                          elem_size, fp8)
 
 
+def conv_plan_variant(direction, G, N, Cin, H, W, Cout, khw, stride, pad,
+                      elem_size, fp8):
+    """Name of the kernel that launcher would launch for this shape, e.g.
+    'conv_fwd_tabled_kernel' or 'conv_bwd_data_s2_kernel' ('<fp8>' appended
+    for the fp8 tile instantiation).  Tells the tabled gather kernels
+    (HETEROFL_CONV_TABLED, on by default) from the untabled ones, which
+    conv_plan's route string does not."""
+    ext = require_native()
+    return ext.conv_plan_variant(direction, G, N, Cin, H, W, Cout, khw,
+                                 stride, pad, elem_size, fp8)
+
+
 # ------------------------------------------------- large-batch inference ops
 def large_conv_supported(k, stride, pad):
     """Shapes conv_fwd_large implements: 3x3/pad 1 and 1x1/pad 0, stride 1
