@@ -29,12 +29,13 @@ of pre-masked windows with
     linears       bf16 F.linear on the encoder and decoder.linear1 (the
                   library-GEMM decision of VERDICT.md K7); linear_q/k/v are
                   concatenated into one E -> 3E projection
-    head          lm_head_ce (ops/csrc/lm_head_ce.hip): vocabulary projection
+    head          lm_head_ce (ops/csrc/lm_head.hip): vocabulary projection
                   fused with the cross-entropy, no (M, V) logits; or the
                   two-step bf16 F.linear + lm_ce_fwd where the router
                   (ops.fused.lm_head_route) measured that faster
-    fill-mask     lm_head_topk (ops/csrc/lm_head_topk.hip): window_topk and
-                  fill_mask take every position's k <= 8 most likely tokens,
+    fill-mask     lm_head_topk (the same kernel with per-lane candidate
+                  lists): window_topk and fill_mask take every position's
+                  k <= 8 most likely tokens,
                   their log-probabilities and the label's NLL from one
                   vocabulary pass, again without (M, V) logits; it is the
                   only route (no two-step top-k measured faster, see

@@ -11,9 +11,6 @@
 // Fragment layout as in conv_mfma.hip (verified by mfma_probe).
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
 constexpr int SMAX = 64;   // bptt
 constexpr int DMAX = 32;   // head_dim
 constexpr int ALDK = 40;   // padded k-stride (elems)

@@ -5,6 +5,11 @@
 
 #define WAVE 64
 
+// MFMA operand / accumulator vectors and the 16-byte bf16 load
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
+
 // fp32 accumulate load for fp32 / bf16 tensors
 template <typename T>
 __device__ __forceinline__ float ld_f32(const T* p) { return (float)*p; }

@@ -32,9 +32,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 typedef unsigned short u16;
 
 constexpr int LBK = 32;          // K-slab

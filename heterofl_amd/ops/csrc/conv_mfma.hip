@@ -51,9 +51,6 @@
 // and were removed; commit 67e6a3a is the last that carries them.
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
 constexpr int BM = 64;
 constexpr int BP = 64;
 constexpr int BK = 32;

@@ -21,7 +21,6 @@
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f4;
-typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 
 __device__ __forceinline__ float bits2f(unsigned short v) {
     return __uint_as_float((unsigned)v << 16);

@@ -348,9 +348,9 @@ def lm_head_ce(x, packed, bias, labels, vocab_mask, V, E, splits=0):
     logit = x . W^T + b in fp32; a vocab-masked column's logit is exactly 0
     (bias included) and still takes part in the softmax, as in
     models/functional.py; the (M, V) logits are never written on the GPU
-    path (ops/csrc/lm_head_ce.hip, bf16 x).  `splits` cuts the vocabulary
-    over that many blocks per row tile (0: the host fills the GPU); for a
-    given value the result is bit-reproducible."""
+    path (ops/csrc/lm_head.hip, KC = 0, bf16 x).  `splits` cuts the
+    vocabulary over that many blocks per row tile (0: the host fills the
+    GPU); for a given value the result is bit-reproducible."""
     if use_native(x):
         ext = require_native()
         none = torch.Tensor()
@@ -385,7 +385,8 @@ def lm_head_topk(x, packed, bias, labels, vocab_mask, V, E, k, splits=0):
     largest logits in descending order, among equal logits the lower column
     first; log-probabilities are top_val - row_lse[:, None].  On the GPU one
     pass over the vocabulary keeps a running top-k next to the running
-    log-sum-exp (ops/csrc/lm_head_topk.hip); `splits` as in lm_head_ce, and
+    log-sum-exp (ops/csrc/lm_head.hip, lm_head_ce's kernel with per-lane
+    lists of capacity KC >= k); `splits` as in lm_head_ce, and
     for a given value the four outputs are bit-reproducible.  On the CPU, and
     under HETEROFL_FORCE_EAGER=1, fp32 logits and a stable descending sort:
     the numerics oracle.

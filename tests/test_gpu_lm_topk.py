@@ -165,15 +165,21 @@ def test_lm_head_topk_rejects_bad_k():
 @pytest.mark.parametrize('splits', [1, 3])
 @pytest.mark.parametrize('shape', HEAD_CASES)
 def test_lm_head_ce_unchanged_next_to_topk(shape, splits, extras):
-    """Guard only (the two kernels share no code, but the same extension):
-    lm_head_ce still meets its host reference."""
+    """lm_head_ce is the top-k kernel instantiated without lists: it still
+    meets its host reference, and on the first three shapes its (row_nll,
+    row_lse) at the same explicit `splits` are bit-equal to lm_head_topk's
+    for k = 1 and k = 5."""
     M, E, V = shape
     case = _head_case(shape, extras)
-    _, (nll, lse) = _run_head(case, shape, splits)
+    args, (nll, lse) = _run_head(case, shape, splits)
     tail = V * 2.0 ** -24 + 1e-5
     e_nll = (nll.cpu() - case['nll']).abs() - (2 * case['delta'] + tail)
     e_lse = (lse.cpu() - case['lse']).abs() - (case['delta'] + tail)
     assert e_nll.max().item() <= 0 and e_lse.max().item() <= 0
+    if shape in HEAD_CASES[:3]:
+        for k in (1, 5):
+            _, _, lse_k, nll_k = lm_head_topk(*args, k, splits=splits)
+            assert torch.equal(nll, nll_k) and torch.equal(lse, lse_k), k
 
 
 # -------------------------------------------------------- NativeLMInference

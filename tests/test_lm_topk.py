@@ -8,7 +8,7 @@ import torch
 from heterofl_amd.fed.infer import NativeLMInference
 from heterofl_amd.logger import Logger
 from heterofl_amd.models import make_model
-from heterofl_amd.ops.fused import lm_head_pack, lm_head_topk
+from heterofl_amd.ops.fused import lm_head_ce, lm_head_pack, lm_head_topk
 from tests.conftest import make_cfg
 from tests.test_lm_infer import LEVELS, _lm_runner
 
@@ -72,6 +72,29 @@ def test_lm_head_topk_torch_path(masked):
     for bad in (0, 9, V + 1):
         with pytest.raises(ValueError):
             lm_head_topk(x, packed, b, labels, mask, V, E, bad)
+
+
+@pytest.mark.parametrize('extras', [False, True])
+def test_lm_head_ce_and_topk_describe_the_same_logits(extras):
+    """The torch paths of the two entry points return equal lse / nll for
+    the same inputs (one ragged tile: M = 7, E = 16, V = 33)."""
+    M, E, V = 7, 16, 33
+    g = torch.Generator().manual_seed(M + E + V)
+    x = torch.randn(M, E, generator=g)
+    w = torch.randn(V, E, generator=g) * 0.2
+    labels = torch.randint(0, V, (M,), generator=g)
+    bias = mask = None
+    if extras:
+        bias = torch.randn(V, generator=g)
+        mask = (torch.rand(V, generator=g) < 0.5).float()
+        mask[labels[0]] = 0        # a masked label
+    packed = lm_head_pack(w, bias)
+    nll, lse = lm_head_ce(x, packed, bias, labels, mask, V, E)
+    assert nll.shape == (M,) and lse.shape == (M,)
+    for k in (1, 5, 8):
+        _, _, lse_k, nll_k = lm_head_topk(x, packed, bias, labels, mask, V,
+                                          E, k)
+        assert torch.equal(lse, lse_k) and torch.equal(nll, nll_k), k
 
 
 def test_lm_head_topk_k_equals_v():
