@@ -6,6 +6,8 @@ std::vector<at::Tensor> bn_relu_fwd(at::Tensor x, at::Tensor gamma,
 std::vector<at::Tensor> bn_relu_bwd(at::Tensor dy, at::Tensor x,
                                     at::Tensor gamma, at::Tensor beta,
                                     at::Tensor mean, at::Tensor invstd);
+std::string bn_relu_route(const std::string& direction, int64_t N, int64_t C,
+                          int64_t HW, int64_t elem_size, bool aligned);
 std::vector<at::Tensor> gn_relu_fwd(at::Tensor x, at::Tensor gamma,
                                     at::Tensor beta, int64_t G, double eps);
 std::vector<at::Tensor> gn_relu_bwd(at::Tensor dy, at::Tensor x,
@@ -115,6 +117,9 @@ int64_t lm_head_topk_splits(int64_t M, int64_t V);
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bn_relu_fwd", &bn_relu_fwd, "fused sBN+ReLU forward");
     m.def("bn_relu_bwd", &bn_relu_bwd, "fused sBN+ReLU backward");
+    m.def("bn_relu_route", &bn_relu_route,
+          "name of the kernel route bn_relu_fwd / bn_relu_bwd would take; "
+          "launches nothing");
     m.def("gn_relu_fwd", &gn_relu_fwd, "fused GroupNorm+ReLU forward");
     m.def("gn_relu_bwd", &gn_relu_bwd, "fused GroupNorm+ReLU backward");
     m.def("masked_ce_fwd", &masked_ce_fwd, "batched masked CE forward");

@@ -354,6 +354,100 @@ conv_out_reduce_kernel(const float* __restrict__ partial,
     st_f32(out + i, v);
 }
 
+// Four consecutive outputs per lane of a split reduce: the slabs' float4 at
+// vector index i4, RED_U loads issued before the first add, each output still
+// adding its partials in sp = 0, 1, ... order from 0.f (the bits of the
+// one-float-per-lane kernels, which HETEROFL_STREAM_VEC=0 runs).
+constexpr int RED_U = 8;
+
+__device__ __forceinline__ float4 sum_slabs_f4(const float4* __restrict__ p,
+                                               long stride4, int split) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    int sp = 0;
+    for (; sp + RED_U <= split; sp += RED_U) {
+        float4 a[RED_U];
+#pragma unroll
+        for (int u = 0; u < RED_U; ++u) a[u] = p[(sp + u) * stride4];
+#pragma unroll
+        for (int u = 0; u < RED_U; ++u) {
+            s.x += a[u].x;
+            s.y += a[u].y;
+            s.z += a[u].z;
+            s.w += a[u].w;
+        }
+    }
+    if (sp + 4 <= split) {
+        float4 a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] = p[(sp + u) * stride4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            s.x += a[u].x;
+            s.y += a[u].y;
+            s.z += a[u].z;
+            s.w += a[u].w;
+        }
+        sp += 4;
+    }
+    if (sp + 2 <= split) {
+        const float4 a0 = p[sp * stride4], a1 = p[(sp + 1) * stride4];
+        s.x += a0.x; s.y += a0.y; s.z += a0.z; s.w += a0.w;
+        s.x += a1.x; s.y += a1.y; s.z += a1.z; s.w += a1.w;
+        sp += 2;
+    }
+    if (sp < split) {
+        const float4 a0 = p[sp * stride4];
+        s.x += a0.x; s.y += a0.y; s.z += a0.z; s.w += a0.w;
+    }
+    return s;
+}
+
+// BIAS: 0 none (every bwd-data call, bias-free fwd): no channel arithmetic;
+// 1: chanstride % 4 == 0, one channel per vector; 2: a vector may straddle
+// channels, one index per element.  IDX is int when total < 2^31.
+// Needs total % 4 == 0, 16-byte aligned partial, 4-element aligned
+// residual / out.
+template <typename T, int BIAS, typename IDX>
+__global__ void __launch_bounds__(256)
+conv_out_reduce_vec_kernel(const float* __restrict__ partial,
+                           const float* __restrict__ bias,
+                           const T* __restrict__ residual,
+                           T* __restrict__ out, long total, long chanstride,
+                           int nchan, int splitk) {
+    const long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total4 = total >> 2;
+    if (i4 >= total4) return;
+    const float4 s = sum_slabs_f4((const float4*)partial + i4, total4, splitk);
+    float v[4] = {s.x, s.y, s.z, s.w};
+    if (BIAS == 1) {
+        const float bv =
+            bias[((IDX)(i4 * 4) / (IDX)chanstride) % (IDX)nchan];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] += bv;
+    } else if (BIAS == 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            v[e] += bias[((IDX)(i4 * 4 + e) / (IDX)chanstride) % (IDX)nchan];
+    }
+    if (sizeof(T) == 4) {
+        if (residual) {
+            const float4 r = ((const float4*)residual)[i4];
+            v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
+        }
+        ((float4*)out)[i4] = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        if (residual) {
+            const uint2 r = ((const uint2*)residual)[i4];
+            v[0] += __uint_as_float(r.x << 16);
+            v[1] += __uint_as_float(r.x & 0xffff0000u);
+            v[2] += __uint_as_float(r.y << 16);
+            v[3] += __uint_as_float(r.y & 0xffff0000u);
+        }
+        ((uint2*)out)[i4] = make_uint2(pack_bf16x2(v[0], v[1]),
+                                       pack_bf16x2(v[2], v[3]));
+    }
+}
+
 // -------------------------------------------------------- bwd-data kernel
 template <typename T, typename TA, typename TB>
 __global__ void __launch_bounds__(256)
@@ -746,6 +840,17 @@ splitp_reduce_kernel(const float* __restrict__ partials,
     float s = 0.f;
     for (int sp = 0; sp < splitp; ++sp) s += partials[(long)sp * GK + i];
     dw[i] = s;
+}
+
+// GK % 4 == 0 and 16-byte aligned bases: four outputs per lane
+__global__ void __launch_bounds__(256)
+splitp_reduce_vec_kernel(const float* __restrict__ partials,
+                         float* __restrict__ dw, long GK, int splitp) {
+    const long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long GK4 = GK >> 2;
+    if (i4 >= GK4) return;
+    ((float4*)dw)[i4] = sum_slabs_f4((const float4*)partials + i4, GK4,
+                                     splitp);
 }
 
 
@@ -2619,6 +2724,35 @@ std::string conv_plan_variant(
     else if ((t) == at::kBFloat16) { using scalar_t = __hip_bfloat16; __VA_ARGS__; } \
     else { TORCH_CHECK(false, "unsupported dtype"); }
 
+// Split-K reduce of fwd / bwd-data: the float4 kernel when the tensor is a
+// whole number of 4-element vectors at aligned bases, else (and with
+// HETEROFL_STREAM_VEC=0) the one-float-per-lane kernel for the whole tensor.
+template <typename T>
+static void launch_out_reduce(hipStream_t stream, const float* pp,
+                              const float* bp, const T* rp, T* yp, long total,
+                              long chanstride, int nchan, int split) {
+    const bool vec = stream_vec_on() && total % 4 == 0 &&
+                     ptr_aligned(pp, 16) && ptr_aligned(yp, 4 * sizeof(T)) &&
+                     (!rp || ptr_aligned(rp, 4 * sizeof(T)));
+    if (!vec) {
+        hipLaunchKernelGGL(conv_out_reduce_kernel<T>,
+                           dim3((int)((total + 255) / 256)), dim3(256), 0,
+                           stream, pp, bp, rp, yp, total, chanstride, nchan,
+                           split);
+        return;
+    }
+    const bool wide = total >= (1L << 31);
+    auto kern = !bp ? conv_out_reduce_vec_kernel<T, 0, int>
+                : chanstride % 4 == 0
+                    ? (wide ? conv_out_reduce_vec_kernel<T, 1, long>
+                            : conv_out_reduce_vec_kernel<T, 1, int>)
+                    : (wide ? conv_out_reduce_vec_kernel<T, 2, long>
+                            : conv_out_reduce_vec_kernel<T, 2, int>);
+    hipLaunchKernelGGL(kern, dim3((int)((total / 4 + 255) / 256)), dim3(256),
+                       0, stream, pp, bp, rp, yp, total, chanstride, nchan,
+                       split);
+}
+
 // The non-resident kernels of a direction share a signature: pick by plan.
 // fp8 tiles are instantiated for bf16 tensors only.
 template <typename T>
@@ -2695,10 +2829,9 @@ at::Tensor conv_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
         }
         if (pl.split > 1) {
             const long total = y.numel();
-            hipLaunchKernelGGL(conv_out_reduce_kernel<scalar_t>,
-                               dim3((int)((total + 255) / 256)), dim3(256), 0,
-                               stream, pp, bp, rp, yp, total,
-                               (long)gm.OH * gm.OW, gm.G * gm.Cout, pl.split);
+            launch_out_reduce<scalar_t>(stream, pp, bp, rp, yp, total,
+                                        (long)gm.OH * gm.OW, gm.G * gm.Cout,
+                                        pl.split);
         }
     });
     return y;
@@ -2753,10 +2886,8 @@ at::Tensor conv_bwd_data(at::Tensor dy, at::Tensor w, int64_t groups,
         }
         if (pl.split > 1) {
             const long total = dx.numel();
-            hipLaunchKernelGGL(conv_out_reduce_kernel<scalar_t>,
-                               dim3((int)((total + 255) / 256)), dim3(256), 0,
-                               stream, pp, nullptr, nullptr, dxp, total, 1L,
-                               1, pl.split);
+            launch_out_reduce<scalar_t>(stream, pp, nullptr, nullptr, dxp,
+                                        total, 1L, 1, pl.split);
         }
     });
     return dx;
@@ -2807,10 +2938,19 @@ at::Tensor conv_bwd_weight(at::Tensor dy, at::Tensor x, int64_t groups,
                                pl.split);
         }
     });
-    if (pl.split > 1)
-        hipLaunchKernelGGL(splitp_reduce_kernel,
-                           dim3((int)((GK + 255) / 256)), dim3(256), 0,
-                           stream, out, dw.data_ptr<float>(), GK, pl.split);
+    if (pl.split > 1) {
+        if (stream_vec_on() && GK % 4 == 0 && aligned16(out) &&
+            aligned16(dw.data_ptr<float>()))
+            hipLaunchKernelGGL(splitp_reduce_vec_kernel,
+                               dim3((int)((GK / 4 + 255) / 256)), dim3(256),
+                               0, stream, out, dw.data_ptr<float>(), GK,
+                               pl.split);
+        else
+            hipLaunchKernelGGL(splitp_reduce_kernel,
+                               dim3((int)((GK + 255) / 256)), dim3(256), 0,
+                               stream, out, dw.data_ptr<float>(), GK,
+                               pl.split);
+    }
     return dw;
 }
 

@@ -201,6 +201,186 @@ bn_relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
     }
 }
 
+// ------------------------------------------- staged BN, 16 bytes per lane
+// The staged kernels above with the memory passes rewritten: the channel's
+// N rows of HW elements come in as dwordx4 loads (BN_VEC_U in flight per lane
+// and tensor before the first LDS write) and go raw into the LDS stage; the
+// normalize / dx pass reads the stage and stores 16 bytes at a time.  The
+// reduction in between is the old one, operand for operand: lane t sums
+// stage[t + 256 k], k ascending, then block_reduce2 (the backward leaves dy
+// raw in the stage and rebuilds the relu mask from x in the dx pass: the
+// same value); so every output has the bits of bn_relu_{fwd,bwd}_kernel<T, true> (HETEROFL_STREAM_VEC=0 runs
+// those).  Needs HW * sizeof(T) % 16 == 0 and 16-byte aligned bases.
+constexpr int BN_VEC_U = 4;
+
+// a lane's vector index t + 256 k as (sample n, vector j of its row),
+// advanced without a divide
+struct RowWalk {
+    int n, j, dn, dj, vpr;
+    __device__ __forceinline__ RowWalk(int v, int vpr_) : vpr(vpr_) {
+        n = v / vpr;
+        j = v - n * vpr;
+        dn = 256 / vpr;
+        dj = 256 - dn * vpr;
+    }
+    __device__ __forceinline__ void step() {
+        j += dj;
+        n += dn;
+        if (j >= vpr) {
+            j -= vpr;
+            ++n;
+        }
+    }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+bn_relu_fwd_vec_kernel(const T* __restrict__ x,
+                       const float* __restrict__ gamma,
+                       const float* __restrict__ beta, T* __restrict__ y,
+                       float* __restrict__ mean_out,
+                       float* __restrict__ invstd_out, int N, int C, int HW,
+                       float eps) {
+    constexpr int V = 16 / sizeof(T);
+    const int c = blockIdx.x;
+    __shared__ float scratch[2 * 256 / WAVE];
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const T* stage = (const T*)smem;
+    uint4* stage4 = (uint4*)smem;
+    const int M = N * HW;
+    const int nvec = M / V;
+    const long samp_stride = (long)C * HW;
+    const T* xc = x + (long)c * HW;
+    T* yc = y + (long)c * HW;
+    RowWalk rw(threadIdx.x, HW / V);
+    for (int v0 = threadIdx.x; v0 < nvec; v0 += 256 * BN_VEC_U) {
+        uint4 r[BN_VEC_U];
+        const long off0 = rw.n * samp_stride + rw.j * V;
+#pragma unroll
+        for (int u = 0; u < BN_VEC_U; ++u) {
+            // past the end: the lane's first vector again, never written
+            const long off = v0 + u * 256 < nvec
+                                 ? rw.n * samp_stride + rw.j * V : off0;
+            r[u] = *(const uint4*)(xc + off);
+            rw.step();
+        }
+#pragma unroll
+        for (int u = 0; u < BN_VEC_U; ++u)
+            if (v0 + u * 256 < nvec) stage4[v0 + u * 256] = r[u];
+    }
+    __syncthreads();
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll 8
+    for (int i = threadIdx.x; i < M; i += 256) {
+        const float v = (float)stage[i];
+        s1 += v;
+        s2 += v * v;
+    }
+    block_reduce2(s1, s2, scratch);
+    const float inv_m = 1.f / (N * HW);
+    const float mean = s1 * inv_m;
+    const float var = fmaxf(s2 * inv_m - mean * mean, 0.f);
+    const float invstd = rsqrtf(var + eps);
+    if (threadIdx.x == 0) {
+        mean_out[c] = mean;
+        invstd_out[c] = invstd;
+    }
+    const float g = gamma ? gamma[c] : 1.f;
+    const float b = beta ? beta[c] : 0.f;
+    const float scale = invstd * g;
+    const float shift = b - mean * scale;
+    RowWalk ww(threadIdx.x, HW / V);
+    for (int v = threadIdx.x; v < nvec; v += 256) {
+        float f[V];
+        unpack16<T>(stage4[v], f);
+#pragma unroll
+        for (int e = 0; e < V; ++e) f[e] = fmaxf(f[e] * scale + shift, 0.f);
+        *(uint4*)(yc + ww.n * samp_stride + ww.j * V) = pack16<T>(f);
+        ww.step();
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+bn_relu_bwd_vec_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                       const float* __restrict__ gamma,
+                       const float* __restrict__ beta,
+                       const float* __restrict__ mean,
+                       const float* __restrict__ invstd, T* __restrict__ dx,
+                       float* __restrict__ dgamma, float* __restrict__ dbeta,
+                       int N, int C, int HW) {
+    constexpr int V = 16 / sizeof(T);
+    const int c = blockIdx.x;
+    __shared__ float scratch[2 * 256 / WAVE];
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int M = N * HW;
+    const int nvec = M / V;
+    const T* sx = (const T*)smem;
+    const T* sd = sx + M;
+    uint4* sx4 = (uint4*)sx;
+    uint4* sd4 = (uint4*)sd;
+    const long samp_stride = (long)C * HW;
+    const T* xc = x + (long)c * HW;
+    const T* dyc = dy + (long)c * HW;
+    T* dxc = dx + (long)c * HW;
+    const float m = mean[c], is = invstd[c];
+    const float g = gamma ? gamma[c] : 1.f;
+    const float b = beta ? beta[c] : 0.f;
+    RowWalk rw(threadIdx.x, HW / V);
+    for (int v0 = threadIdx.x; v0 < nvec; v0 += 256 * BN_VEC_U) {
+        uint4 rx[BN_VEC_U], rd[BN_VEC_U];
+        const long off0 = rw.n * samp_stride + rw.j * V;
+#pragma unroll
+        for (int u = 0; u < BN_VEC_U; ++u) {
+            const long off = v0 + u * 256 < nvec
+                                 ? rw.n * samp_stride + rw.j * V : off0;
+            rx[u] = *(const uint4*)(xc + off);
+            rd[u] = *(const uint4*)(dyc + off);
+            rw.step();
+        }
+#pragma unroll
+        for (int u = 0; u < BN_VEC_U; ++u)
+            if (v0 + u * 256 < nvec) {
+                sx4[v0 + u * 256] = rx[u];
+                sd4[v0 + u * 256] = rd[u];
+            }
+    }
+    __syncthreads();
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll 8
+    for (int i = threadIdx.x; i < M; i += 256) {
+        const float xh = ((float)sx[i] - m) * is;
+        const float pre = xh * g + b;
+        const float d = pre > 0.f ? ld_f32(sd + i) : 0.f;
+        s1 += d;
+        s2 += d * xh;
+    }
+    block_reduce2(s1, s2, scratch);
+    if (threadIdx.x == 0) {
+        dbeta[c] = s1;
+        dgamma[c] = s2;
+    }
+    const float inv_M = 1.f / (N * HW);
+    const float k1 = s1 * inv_M, k2 = s2 * inv_M;
+    const float gis = g * is;
+    RowWalk ww(threadIdx.x, HW / V);
+    for (int v = threadIdx.x; v < nvec; v += 256) {
+        float fx[V], fd[V];
+        unpack16<T>(sx4[v], fx);
+        unpack16<T>(sd4[v], fd);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            // the relu mask again from x: d is dy's value or 0 either way
+            const float xh = (fx[e] - m) * is;
+            const float pre = xh * g + b;
+            const float d = pre > 0.f ? fd[e] : 0.f;
+            fd[e] = gis * (d - k1 - xh * k2);
+        }
+        *(uint4*)(dxc + ww.n * samp_stride + ww.j * V) = pack16<T>(fd);
+        ww.step();
+    }
+}
+
 // ---------------------------------------------------------------- GroupNorm
 // Stats per (sample n, group j) over the group's channels x HW
 // (covers gn=4 / ln=1 / in=C groups, reference: src/models/resnet.py:19-26).
@@ -314,6 +494,33 @@ gn_relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
     else if ((t) == at::kBFloat16) { using scalar_t = __hip_bfloat16; __VA_ARGS__; } \
     else { TORCH_CHECK(false, "unsupported dtype"); }
 
+// Which kernel a BN+ReLU call takes.  split3: forward over 64 K elements per
+// channel; direct: the channel is over the 64 KB LDS stage (bwd stages x and
+// dy); vec: the staged case with 16-byte rows and bases
+// (HETEROFL_STREAM_VEC=0 turns it off); staged: everything else, e.g. 7x7
+// planes, 14x14 in bf16, a view that starts mid-buffer.
+enum BnRoute { BN_VEC, BN_STAGED, BN_DIRECT, BN_SPLIT3 };
+
+static BnRoute bn_route(bool bwd, long N, long HW, int esz, bool aligned) {
+    const long M = N * HW;
+    if (!bwd && M > 64 * 1024) return BN_SPLIT3;
+    if ((bwd ? 2 : 1) * M * esz > 64 * 1024) return BN_DIRECT;
+    if (stream_vec_on() && aligned && (HW * esz) % 16 == 0) return BN_VEC;
+    return BN_STAGED;
+}
+
+// route name for bn_relu_fwd / bn_relu_bwd (direction "fwd" / "bwd");
+// launches nothing.  C does not enter the decision.
+std::string bn_relu_route(const std::string& direction, int64_t N, int64_t C,
+                          int64_t HW, int64_t elem_size, bool aligned) {
+    TORCH_CHECK(direction == "fwd" || direction == "bwd",
+                "direction must be fwd or bwd");
+    (void)C;
+    static const char* names[] = {"vec", "staged", "direct", "split3"};
+    return names[bn_route(direction == "bwd", N, HW, (int)elem_size,
+                          aligned)];
+}
+
 std::vector<at::Tensor> bn_relu_fwd(at::Tensor x, at::Tensor gamma,
                                     at::Tensor beta, double eps) {
     TORCH_CHECK(x.is_cuda() && x.is_contiguous());
@@ -355,31 +562,20 @@ std::vector<at::Tensor> bn_relu_fwd(at::Tensor x, at::Tensor gamma,
         });
         return {y, mean, invstd};
     }
+    const BnRoute route = bn_route(false, N, HW, (int)x.element_size(),
+                                   ptr_aligned(x.data_ptr(), 16) &&
+                                       ptr_aligned(y.data_ptr(), 16));
+    const float* gp = gamma.defined() ? gamma.data_ptr<float>() : nullptr;
+    const float* bp = beta.defined() ? beta.data_ptr<float>() : nullptr;
     DISPATCH_FT(x.scalar_type(), {
-        if (stage_bytes <= 64 * 1024)
-            hipLaunchKernelGGL((bn_relu_fwd_kernel<scalar_t, true>), dim3(C),
-                               dim3(256), (int)stage_bytes, stream,
-                               (const scalar_t*)x.data_ptr(),
-                               gamma.defined() ? gamma.data_ptr<float>()
-                                               : nullptr,
-                               beta.defined() ? beta.data_ptr<float>()
-                                              : nullptr,
-                               (scalar_t*)y.data_ptr(),
-                               mean.data_ptr<float>(),
-                               invstd.data_ptr<float>(), N, C, HW,
-                               (float)eps);
-        else
-            hipLaunchKernelGGL((bn_relu_fwd_kernel<scalar_t, false>), dim3(C),
-                               dim3(256), 0, stream,
-                               (const scalar_t*)x.data_ptr(),
-                               gamma.defined() ? gamma.data_ptr<float>()
-                                               : nullptr,
-                               beta.defined() ? beta.data_ptr<float>()
-                                              : nullptr,
-                               (scalar_t*)y.data_ptr(),
-                               mean.data_ptr<float>(),
-                               invstd.data_ptr<float>(), N, C, HW,
-                               (float)eps);
+        auto kern = route == BN_VEC ? bn_relu_fwd_vec_kernel<scalar_t>
+                    : route == BN_STAGED ? bn_relu_fwd_kernel<scalar_t, true>
+                                         : bn_relu_fwd_kernel<scalar_t, false>;
+        hipLaunchKernelGGL(kern, dim3(C), dim3(256),
+                           route == BN_DIRECT ? 0 : (int)stage_bytes, stream,
+                           (const scalar_t*)x.data_ptr(), gp, bp,
+                           (scalar_t*)y.data_ptr(), mean.data_ptr<float>(),
+                           invstd.data_ptr<float>(), N, C, HW, (float)eps);
     });
     return {y, mean, invstd};
 }
@@ -396,35 +592,23 @@ std::vector<at::Tensor> bn_relu_bwd(at::Tensor dy, at::Tensor x,
     auto dyc = dy.contiguous();
     auto stream = at::hip::getCurrentHIPStream();
     const long stage_bytes = 2L * N * (x.numel() / (N * C)) * x.element_size();
+    const BnRoute route = bn_route(true, N, HW, (int)x.element_size(),
+                                   ptr_aligned(x.data_ptr(), 16) &&
+                                       ptr_aligned(dyc.data_ptr(), 16) &&
+                                       ptr_aligned(dx.data_ptr(), 16));
+    const float* gp = gamma.defined() ? gamma.data_ptr<float>() : nullptr;
+    const float* bp = beta.defined() ? beta.data_ptr<float>() : nullptr;
     DISPATCH_FT(x.scalar_type(), {
-        if (stage_bytes <= 64 * 1024)
-            hipLaunchKernelGGL((bn_relu_bwd_kernel<scalar_t, true>), dim3(C),
-                               dim3(256), (int)stage_bytes, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               (const scalar_t*)x.data_ptr(),
-                               gamma.defined() ? gamma.data_ptr<float>()
-                                               : nullptr,
-                               beta.defined() ? beta.data_ptr<float>()
-                                              : nullptr,
-                               mean.data_ptr<float>(),
-                               invstd.data_ptr<float>(),
-                               (scalar_t*)dx.data_ptr(),
-                               dgamma.data_ptr<float>(),
-                               dbeta.data_ptr<float>(), N, C, HW);
-        else
-            hipLaunchKernelGGL((bn_relu_bwd_kernel<scalar_t, false>), dim3(C),
-                               dim3(256), 0, stream,
-                               (const scalar_t*)dyc.data_ptr(),
-                               (const scalar_t*)x.data_ptr(),
-                               gamma.defined() ? gamma.data_ptr<float>()
-                                               : nullptr,
-                               beta.defined() ? beta.data_ptr<float>()
-                                              : nullptr,
-                               mean.data_ptr<float>(),
-                               invstd.data_ptr<float>(),
-                               (scalar_t*)dx.data_ptr(),
-                               dgamma.data_ptr<float>(),
-                               dbeta.data_ptr<float>(), N, C, HW);
+        auto kern = route == BN_VEC ? bn_relu_bwd_vec_kernel<scalar_t>
+                    : route == BN_STAGED ? bn_relu_bwd_kernel<scalar_t, true>
+                                         : bn_relu_bwd_kernel<scalar_t, false>;
+        hipLaunchKernelGGL(kern, dim3(C), dim3(256),
+                           route == BN_DIRECT ? 0 : (int)stage_bytes, stream,
+                           (const scalar_t*)dyc.data_ptr(),
+                           (const scalar_t*)x.data_ptr(), gp, bp,
+                           mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                           (scalar_t*)dx.data_ptr(), dgamma.data_ptr<float>(),
+                           dbeta.data_ptr<float>(), N, C, HW);
     });
     return {dx, dgamma, dbeta};
 }

@@ -48,6 +48,19 @@ def fused_norm_relu(x, weight, bias, kind, groups=1, eps=1e-5):
     return _FusedNormReLU.apply(x, weight, bias, kind, groups, eps)
 
 
+def bn_relu_route(direction, N, C, HW, elem_size, aligned=True):
+    """Route bn_relu_fwd / bn_relu_bwd (direction 'fwd' / 'bwd') take for an
+    (N, C, HW) tensor of elem_size bytes per element; the launchers' own rule,
+    nothing is launched.  'vec': the staged kernel with 16-byte global and
+    LDS accesses (HW * elem_size a multiple of 16, every base 16-byte
+    aligned - pass aligned=False for a view that is not;
+    HETEROFL_STREAM_VEC=0 turns it off); 'staged': the element-wise staged
+    kernel; 'direct': the channel is over the 64 KB LDS stage; 'split3': the
+    large-batch 3-kernel forward."""
+    ext = require_native()
+    return ext.bn_relu_route(direction, N, C, HW, elem_size, aligned)
+
+
 def eager_scaler_norm_relu(x, weight, bias, kind, groups, rate, eps=1e-5):
     """Reference path: scaler -> norm -> relu with explicit torch ops."""
     if rate != 1.0:
