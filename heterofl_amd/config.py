@@ -67,6 +67,11 @@ _DEFAULT = {
     'native_ops': True,
     # Capture the local-training step in a hipGraph on GPU.
     'hip_graphs': True,
+    # Sub-model extraction: 'static' hands every client the first channels
+    # of each layer; 'roll' moves the extraction window by roll_step
+    # positions per round so all global channels are trained evenly.
+    'submodel': 'static',
+    'roll_step': 1,
 }
 
 

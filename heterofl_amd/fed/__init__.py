@@ -1,6 +1,8 @@
-from .federation import Federation, Axis, ParamSlice, FULL, PREFIX, GATHER
+from .federation import (Federation, Axis, ParamSlice, FULL, PREFIX, GATHER,
+                         ROLL)
 from .runner import FedRunner, sample_active_users
 from .sequential import SequentialClientTrainer
 
 __all__ = ['Federation', 'Axis', 'ParamSlice', 'FULL', 'PREFIX', 'GATHER',
-           'FedRunner', 'sample_active_users', 'SequentialClientTrainer']
+           'ROLL', 'FedRunner', 'sample_active_users',
+           'SequentialClientTrainer']

@@ -139,7 +139,7 @@ class FedRunner:
         with _phase_timer('1.distribute'):
             local_parameters, param_idx = self.federation.distribute(
                 user_idx, resample=resample,
-                slots=my_clients if world > 1 else None)
+                slots=my_clients if world > 1 else None, round=epoch)
 
         with _phase_timer('2.local_train'):
             trained = dict(self.trainer.train_clients(
@@ -455,7 +455,11 @@ class FedRunner:
         'Local-Loss', 'Local-Accuracy'}} and logs each metric under
         'test/<name>@<rate>'; the tracked per-level models stay available in
         self.level_models.  Vision models only.  Multi-rank: every rank
-        computes the identical result redundantly; rank 0 writes."""
+        computes the identical result redundantly; rank 0 writes.
+
+        Under cfg['submodel'] = 'roll' the slices are the windows of round
+        `epoch`: the levels are evaluated as the clients of the round just
+        trained received them."""
         from .. import ops as native_ops
         if self.is_lm:
             raise NotImplementedError(
@@ -468,7 +472,7 @@ class FedRunner:
         self.level_models = {}
         with torch.no_grad():
             for rate in sorted(set(cfg['model_rate']), reverse=True):
-                params = self.federation.slice_for_rate(rate)
+                params = self.federation.slice_for_rate(rate, round=epoch)
                 prev = native_ops.set_large_conv(True)
                 try:
                     test_model = self._stats_model(rate, params)
@@ -654,6 +658,10 @@ class FedRunner:
         the per-level models stay in self.level_models.  Multi-rank: every
         rank computes the identical result redundantly; rank 0 writes.
 
+        Under cfg['submodel'] = 'roll' the slices are the windows of round
+        `epoch`: the levels are evaluated as the clients of the round just
+        trained received them.
+
         HETEROFL_LM_TOPK=k (1..8) adds token accuracy in percent, from the
         same vocabulary pass as the loss: 'Global-Accuracy' and, for k > 1,
         'Global-Accuracy-Top{k}' (label among the first / the first k
@@ -675,7 +683,7 @@ class FedRunner:
             src = self._lm_masked_src(tokens)
             which = list(range(len(windows)))
             for rate in sorted(set(cfg['model_rate']), reverse=True):
-                params = self.federation.slice_for_rate(rate)
+                params = self.federation.slice_for_rate(rate, round=epoch)
                 model = make_model(dict(cfg, global_model_rate=rate),
                                    model_rate=rate).to(cfg['device'])
                 model.load_state_dict(params)

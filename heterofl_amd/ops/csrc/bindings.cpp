@@ -92,6 +92,9 @@ std::vector<at::Tensor> embed_pos_bwd(at::Tensor dy, at::Tensor ids,
                                       int64_t V, int64_t P, double rate);
 std::vector<at::Tensor> maxpool2_fwd(at::Tensor x);
 void pack_slices(at::Tensor blob, int64_t n, int64_t max_rows);
+void pack_slices_roll(at::Tensor spans, int64_t n_spans, at::Tensor blocks);
+void combine_accumulate(at::Tensor table, int64_t n_tensors,
+                        int64_t n_entries, at::Tensor blocks);
 at::Tensor maxpool2_bwd(at::Tensor dy, at::Tensor arg, int64_t H,
                         int64_t W);
 at::Tensor conv_pack_weight(at::Tensor w);
@@ -167,6 +170,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("maxpool2_fwd", &maxpool2_fwd, "2x2/2 MaxPool forward (saves argmax)");
     m.def("pack_slices", &pack_slices,
           "one-launch distribute slice pack from a descriptor table");
+    m.def("pack_slices_roll", &pack_slices_roll,
+          "one-launch distribute pack of periodic-window (rolled / per-head) "
+          "slices");
+    m.def("combine_accumulate", &combine_accumulate,
+          "one-launch deterministic combine accumulator + count (gather "
+          "form)");
     m.def("maxpool2_bwd", &maxpool2_bwd, "2x2/2 MaxPool backward");
     m.def("conv_pack_weight", &conv_pack_weight,
           "one-time tap-major bf16 repack for conv_fwd_large");

@@ -801,3 +801,130 @@ class _FusedEmbedPos(torch.autograd.Function):
 
 def fused_embed_pos(ids, table, pos, t16, p16, rate):
     return _FusedEmbedPos.apply(ids, table, pos, t16, p16, rate)
+
+
+# ------------------------------------------------- combine accumulate (K14)
+COMBINE_PER_BLOCK = 1024   # elements per block (combine.hip)
+_COMBINE_BLOCKS = {}       # (device, shapes) -> (n_blocks, 2) int32 table
+
+
+def _check_window(win, size, what):
+    period, shift, take = win
+    if not (period >= 1 and size % period == 0 and 0 <= shift < period
+            and 1 <= take <= period):
+        raise ValueError('combine_accumulate: bad {} window {} over an axis '
+                         'of {}'.format(what, win, size))
+    return (size // period) * take
+
+
+def combine_accumulate(shapes, clients, device):
+    """The accumulator and count of Federation.accumulate for a set of
+    global tensors from ONE kernel launch (ops/csrc/combine.hip).
+
+    shapes[i] is the global tensor's shape; its dim 0 is the out axis, dim 1
+    (if any) the in axis and the rest `inner`.  clients[i] lists the
+    reporting clients of tensor i in ascending slot order, each
+    (val, out_window, in_window, row_mask): val the client's fp32 slice on
+    `device`, a window (period, shift, take) mapping local index j to global
+    (j // take) * period + (shift + j % take) % period (in_window None for
+    1-D tensors), row_mask None or a uint8 array over the local out rows
+    (the label-split filter of output layers; 0 drops the row).
+
+    Returns ([tmp_i], [cnt_i]), global-shaped fp32, every element written
+    (zeros where nobody contributes).  Clients are added one at a time in
+    list order, so the sums are bit-identical to the torch loop's."""
+    import numpy as np
+    ext = require_native()
+    if ext is None:
+        raise RuntimeError('combine_accumulate is the native route; use '
+                           'Federation.accumulate under HETEROFL_FORCE_EAGER')
+    device = torch.device(device)
+    t_dt = np.dtype([('tmp', 'u8'), ('cnt', 'u8'), ('O', 'i4'), ('I', 'i4'),
+                     ('inner', 'i4'), ('ent_start', 'i4'),
+                     ('ent_count', 'i4'), ('pad', 'i4')])
+    e_dt = np.dtype([('val', 'u8'), ('mask', 'u8'), ('out', 'i4', 3),
+                     ('inp', 'i4', 3), ('n_in', 'i4'), ('pad', 'i4')])
+    assert t_dt.itemsize == 40 and e_dt.itemsize == 48
+    dims, numels = [], []
+    for shape in shapes:
+        shape = tuple(int(s) for s in shape)
+        if len(shape) == 0:
+            shape = (1,)
+        O = shape[0]
+        I = shape[1] if len(shape) > 1 else 1
+        inner = 1
+        for s in shape[2:]:
+            inner *= s
+        if O * I * inner >= 2 ** 31:
+            raise ValueError('combine_accumulate: tensor too large')
+        dims.append((O, I, inner))
+        numels.append(O * I * inner)
+    total = sum(numels)
+    flat_tmp = torch.empty(total, dtype=torch.float32, device=device)
+    flat_cnt = torch.empty(total, dtype=torch.float32, device=device)
+    tensors = np.zeros(len(dims), dtype=t_dt)
+    n_entries = sum(len(c) for c in clients)
+    entries = np.zeros(n_entries, dtype=e_dt)
+    masks, mask_off, keep = [], 0, []
+    mask_rel = np.full(n_entries, -1, dtype=np.int64)
+    e = off = 0
+    tmp_out, cnt_out = [], []
+    for i, ((O, I, inner), shape) in enumerate(zip(dims, shapes)):
+        tmp = flat_tmp[off:off + numels[i]].view(tuple(shape))
+        cnt = flat_cnt[off:off + numels[i]].view(tuple(shape))
+        tmp_out.append(tmp)
+        cnt_out.append(cnt)
+        tensors[i] = (tmp.data_ptr(), cnt.data_ptr(), O, I, inner, e,
+                      len(clients[i]), 0)
+        off += numels[i]
+        for val, ow, iw, mask in clients[i]:
+            if iw is None:
+                iw = (I, 0, I)
+            n_out = _check_window(ow, O, 'out')
+            n_in = _check_window(iw, I, 'in')
+            if not (val.dtype == torch.float32 and val.device == device):
+                raise ValueError('combine_accumulate: client values must be '
+                                 'fp32 on {}'.format(device))
+            if val.numel() != n_out * n_in * inner:
+                raise ValueError(
+                    'combine_accumulate: client slice of {} elements does '
+                    'not match its windows ({} x {} x {})'.format(
+                        val.numel(), n_out, n_in, inner))
+            val = val.contiguous()
+            keep.append(val)
+            if mask is not None:
+                mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+                if mask.size != n_out:
+                    raise ValueError('combine_accumulate: row mask of {} '
+                                     'for {} rows'.format(mask.size, n_out))
+                mask_rel[e] = mask_off
+                masks.append(mask)
+                mask_off += mask.size
+            entries[e] = (val.data_ptr(), 0, tuple(ow), tuple(iw), n_in, 0)
+            e += 1
+    bkey = (str(device), tuple(dims))
+    blocks = _COMBINE_BLOCKS.get(bkey)
+    if blocks is None:
+        rows = [np.stack([np.full((n + COMBINE_PER_BLOCK - 1)
+                                  // COMBINE_PER_BLOCK, i, dtype=np.int32),
+                          np.arange(0, n, COMBINE_PER_BLOCK,
+                                    dtype=np.int32)], 1)
+                for i, n in enumerate(numels) if n]
+        tab = np.concatenate(rows) if rows else np.zeros((0, 2), np.int32)
+        if len(_COMBINE_BLOCKS) >= 16:
+            _COMBINE_BLOCKS.clear()
+        blocks = _COMBINE_BLOCKS[bkey] = \
+            torch.from_numpy(np.ascontiguousarray(tab)).to(device)
+    # one upload: [tensor table | entry table | row masks]
+    mask_base = tensors.nbytes + entries.nbytes
+    table = torch.empty(mask_base + mask_off, dtype=torch.uint8,
+                        device=device)
+    has = mask_rel >= 0
+    entries['mask'][has] = (table.data_ptr() + mask_base
+                            + mask_rel[has]).astype(np.uint64)
+    host = np.concatenate([tensors.view(np.uint8), entries.view(np.uint8)]
+                          + masks)
+    table.copy_(torch.from_numpy(host))
+    ext.combine_accumulate(table, len(dims), n_entries, blocks)
+    del keep
+    return tmp_out, cnt_out
