@@ -382,6 +382,18 @@ bn_relu_bwd_vec_kernel(const T* __restrict__ dy, const T* __restrict__ x,
 }
 
 // ---------------------------------------------------------------- GroupNorm
+// a * b and a - b rounded once each and never contracted into an fma (the
+// _rn arithmetic intrinsics are plain operators to the compiler and contract
+// like them): for where two equal products have to cancel exactly.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 // Stats per (sample n, group j) over the group's channels x HW
 // (covers gn=4 / ln=1 / in=C groups, reference: src/models/resnet.py:19-26).
 template <typename T, bool STAGE>
@@ -409,7 +421,12 @@ gn_relu_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
     block_reduce2(s1, s2, scratch);
     const float inv_m = 1.f / M;
     const float mean = s1 * inv_m;
-    const float var = fmaxf(s2 * inv_m - mean * mean, 0.f);
+    // both products rounded before the subtraction: contracted into one fma
+    // the difference kept the rounding residual of mean^2, and a group of
+    // one element (in: 1x1 planes) got var = 6e-8 x^2 against eps = 1e-5,
+    // invstd 6e-4 off; this way x^2 - x^2 cancels exactly
+    const float var = fmaxf(sub_rn(mul_rn(s2, inv_m), mul_rn(mean, mean)),
+                            0.f);
     const float invstd = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
         mean_out[ng] = mean;
@@ -468,8 +485,12 @@ gn_relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
         const float xh = (ld_f32(x + base + i) - m) * is;
         const float pre = xh * g + b;
         const float d = pre > 0.f ? ld_f32(dy + base + i) : 0.f;
-        s1 += d * g;
-        s2 += d * g * xh;
+        // d * g rounded on its own, here and in the dx pass: k1 is the mean
+        // of these values, and fused into the subtraction below a group of
+        // one element got dx = invstd * (rounding residual of d * g), not 0
+        const float dg = mul_rn(d, g);
+        s1 += dg;
+        s2 += dg * xh;
     }
     block_reduce2(s1, s2, scratch);
     const float inv_M = 1.f / M;
@@ -481,7 +502,8 @@ gn_relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
         const float xh = (ld_f32(x + base + i) - m) * is;
         const float pre = xh * g + b;
         const float d = pre > 0.f ? ld_f32(dy + base + i) : 0.f;
-        st_f32(dx + base + i, is * (d * g - k1 - xh * k2));
+        st_f32(dx + base + i,
+               is * (sub_rn(mul_rn(d, g), k1) - xh * k2));
     }
 }
 
