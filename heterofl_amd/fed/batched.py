@@ -157,6 +157,9 @@ class BNormReLU(nn.Module):
                                                   self.bias, 1e-5)
                 self.stats_sink(self, mean, invstd, x)
                 return y
+            # forward_alias below takes this same route (native, bn, no
+            # stats sink) through fused_norm_relu_alias: keep the conditions
+            # of the two in step
             from ..ops.fused import fused_norm_relu
             return fused_norm_relu(x, self.weight, self.bias, kind,
                                    self.groups)
@@ -168,6 +171,18 @@ class BNormReLU(nn.Module):
         r = self.rate if self.training else 1.0
         return eager_scaler_norm_relu(x, self.weight, self.bias, kind,
                                       self.groups, r)
+
+    def forward_alias(self, x):
+        """(forward(x), x as the block's residual).  On the native BN training
+        path with HETEROFL_STEP_FUSED on, the second value is an alias that
+        routes the residual's gradient into the BN backward kernel
+        (ops.fused._FusedNormReLUAlias); everywhere else it is x itself."""
+        if (self.norm == 'bn' and self.stats_sink is None
+                and native_ops.use_native(x) and native_ops.step_fused_on()
+                and torch.is_grad_enabled() and x.requires_grad):
+            from ..ops.fused import fused_norm_relu_alias
+            return fused_norm_relu_alias(x, self.weight, self.bias)
+        return self.forward(x), x
 
 
 class BMaxPool2(nn.Module):
@@ -209,8 +224,11 @@ class BBlock(nn.Module):
                                     1, stride, 0, bias=False)
 
     def forward(self, x):
-        out = self.n1(x)
-        shortcut = self.shortcut(out) if hasattr(self, 'shortcut') else x
+        if hasattr(self, 'shortcut'):
+            out = self.n1(x)
+            shortcut = self.shortcut(out)
+        else:
+            out, shortcut = self.n1.forward_alias(x)
         out = self.conv1(out)
         # residual add fused into conv2's epilogue on the native path
         return self.conv2(self.n2(out), residual=shortcut)
@@ -237,8 +255,11 @@ class BBottleneck(nn.Module):
                                     1, stride, 0, bias=False)
 
     def forward(self, x):
-        out = self.n1(x)
-        shortcut = self.shortcut(out) if hasattr(self, 'shortcut') else x
+        if hasattr(self, 'shortcut'):
+            out = self.n1(x)
+            shortcut = self.shortcut(out)
+        else:
+            out, shortcut = self.n1.forward_alias(x)
         out = self.conv1(out)
         out = self.conv2(self.n2(out))
         return self.conv3(self.n3(out), residual=shortcut)
@@ -272,14 +293,21 @@ class BatchedResNet(nn.Module):
             self.in_planes = planes * block.expansion
         return nn.Sequential(*layers)
 
-    def forward(self, x):
-        # x: (N, R*data_ch, H, W) -> scores (N, R, classes)
+    def features(self, x):
+        """Everything before the head: (N, R*C, H, W)."""
         out = self.conv1(x)
         out = self.layer1(out)
         out = self.layer2(out)
         out = self.layer3(out)
         out = self.layer4(out)
-        out = self.n4(out)
+        return self.n4(out)
+
+    def head_params(self):
+        return self.linear.weight, self.linear.bias
+
+    def forward(self, x):
+        # x: (N, R*data_ch, H, W) -> scores (N, R, classes)
+        out = self.features(x)
         if native_ops.use_native(out):
             from ..ops.fused import fused_head
             return fused_head(out, self.linear.weight, self.linear.bias,
@@ -314,8 +342,14 @@ class BatchedConv(nn.Module):
         self._feat = hidden_size[-1]
         self.head = BLinear(R, hidden_size[-1], num_classes)
 
+    def features(self, x):
+        return self.blocks(x)
+
+    def head_params(self):
+        return self.head.weight, self.head.bias
+
     def forward(self, x):
-        out = self.blocks(x)
+        out = self.features(x)
         if native_ops.use_native(out):
             from ..ops.fused import fused_head
             return fused_head(out, self.head.weight, self.head.bias, self.R)
@@ -408,6 +442,48 @@ def batched_masked_ce(scores, labels, label_masks, metrics=None):
             metrics[:, 1] += correct
             metrics[:, 2] += N
     return losses
+
+
+def step_losses(model, xb, yb, label_masks, metrics=None, amp=False,
+                fused=None):
+    """Training forward of a batched vision model: (losses (R,), scores
+    (N, R, J)).  fused (default: native device and HETEROFL_STEP_FUSED on)
+    stops the model before its head and runs pool + linear + masked CE as
+    ops.fused.fused_head_ce; otherwise model(xb) then batched_masked_ce.  The
+    graphed step and the eager native step both come through here."""
+    if fused is None:
+        fused = native_ops.use_native(xb) and native_ops.step_fused_on()
+    dev = 'cuda' if xb.is_cuda else 'cpu'
+    if fused:
+        from ..ops.fused import fused_head_ce
+        with torch.autocast(dev, torch.bfloat16, enabled=amp):
+            feat = model.features(xb)
+        w, b = model.head_params()
+        return fused_head_ce(feat, w, b, yb, label_masks, model.R,
+                             metrics=metrics)
+    with torch.autocast(dev, torch.bfloat16, enabled=amp):
+        scores = model(xb)
+    losses = batched_masked_ce(scores.float(), yb, label_masks,
+                               metrics=metrics)
+    return losses, scores
+
+
+def step_grads(losses, params=None, fused=None, ones=None):
+    """d(sum of losses) / d params, returned (params given) or accumulated
+    into .grad (params None).  fused: the sum is never formed; its gradient,
+    exactly ones, goes in as grad_outputs (`ones`: a persistent (R,) tensor,
+    made here if absent)."""
+    if fused is None:
+        fused = native_ops.use_native(losses) and native_ops.step_fused_on()
+    if not fused:
+        if params is None:
+            return losses.sum().backward()
+        return torch.autograd.grad(losses.sum(), params)
+    if ones is None:
+        ones = torch.ones_like(losses)
+    if params is None:
+        return torch.autograd.backward(losses, ones)
+    return torch.autograd.grad(losses, params, grad_outputs=ones)
 
 
 def per_client_clip_(params, R, max_norm=1.0):
@@ -709,10 +785,19 @@ class BatchedClientTrainer:
                     torch._foreach_zero_([p.grad for p in params])
                 else:
                     opt.zero_grad(set_to_none=True)
-                with torch.autocast('cuda', torch.bfloat16, enabled=self._amp):
-                    scores = model(xb)
-                losses = batched_masked_ce(scores.float(), yb, masks)
-                losses.sum().backward()
+                if native:
+                    # the graphed step's forward and backward, launch for
+                    # launch (fed/graphs.py)
+                    fused = native_ops.step_fused_on()
+                    losses, scores = step_losses(model, xb, yb, masks,
+                                                 amp=self._amp, fused=fused)
+                    step_grads(losses, fused=fused)
+                else:
+                    with torch.autocast('cuda', torch.bfloat16,
+                                        enabled=self._amp):
+                        scores = model(xb)
+                    losses = batched_masked_ce(scores.float(), yb, masks)
+                    losses.sum().backward()
                 if native:
                     fopt.step(1.0, lr, cfg['momentum'], cfg['weight_decay'])
                 else:

@@ -23,7 +23,7 @@ new round only repacks buffers and replays.
 import torch
 
 from .. import ops as native_ops
-from .batched import batched_masked_ce
+from .batched import batched_masked_ce, step_grads, step_losses
 
 
 class GraphedGroupStep:
@@ -50,6 +50,10 @@ class GraphedGroupStep:
         self.y_all = torch.zeros(capacity, R, dtype=torch.long, device=device)
         self.masks = torch.ones(R, classes, device=device)
         self.counter = torch.zeros(1, dtype=torch.long, device=device)
+        # batch_gather's ticket word and the gradient of the (unformed) loss
+        # sum: persistent, so the graph reads stable addresses
+        self._ticket = torch.zeros(1, dtype=torch.int32, device=device)
+        self._ones = torch.ones(R, device=device)
         # device metric accumulators: [loss_sum, correct, samples] per client
         self.metrics = torch.zeros(R, 3, device=device)
         self.graph = None
@@ -71,22 +75,32 @@ class GraphedGroupStep:
         return (self.R * in_ch, hw, hw)
 
     def _one_step(self):
-        idx = self.counter * self.batch + self._arange
-        xb = self.x_all.index_select(0, idx)
-        yb = self.y_all.index_select(0, idx)
+        # HETEROFL_STEP_FUSED (read here, so a captured graph keeps the
+        # setting it was captured under): batch fetch + counter bump in one
+        # launch, head + CE in two, no loss sum (its gradient is ones)
+        fused = self._native and native_ops.step_fused_on()
+        if fused:
+            from ..ops.fused import batch_gather
+            xb, yb = batch_gather(self.x_all, self.y_all, self.counter,
+                                  self.batch, self._ticket)
+        else:
+            idx = self.counter * self.batch + self._arange
+            xb = self.x_all.index_select(0, idx)
+            yb = self.y_all.index_select(0, idx)
         if self._native:
-            with torch.autocast('cuda', torch.bfloat16, enabled=self.amp):
-                scores = self.model(xb)
-            losses = batched_masked_ce(scores.float(), yb, self.masks,
-                                       metrics=self.metrics)
-            raw = torch.autograd.grad(losses.sum(), self.params)
+            losses, _ = step_losses(self.model, xb, yb, self.masks,
+                                    metrics=self.metrics, amp=self.amp,
+                                    fused=fused)
+            raw = step_grads(losses, self.params, fused=fused,
+                             ones=self._ones)
             grads = [t if t.is_contiguous() else t.contiguous() for t in raw]
             self._captured_grads = grads
             if not self._capturing:
                 self.opt.bind(grads)  # eager warmup: per-iteration pointers
             self.opt.launch(1.0, self.lr, self.momentum, self.weight_decay)
-            with torch.no_grad():
-                self.counter += 1
+            if not fused:
+                with torch.no_grad():
+                    self.counter += 1
             return
         with torch.autocast('cuda', torch.bfloat16, enabled=self.amp):
             scores = self.model(xb)

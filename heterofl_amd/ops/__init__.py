@@ -65,6 +65,21 @@ def native_conv_enabled():
     return os.environ.get('HETEROFL_NATIVE_CONV', '1') == '1'
 
 
+def step_fused_on():
+    """HETEROFL_STEP_FUSED (default on, read on every call; '0' = off): the
+    vision step's classifier tail in two launches (ops/csrc/head_ce.hip), its
+    batch fetch in one (batch_gather.hip) and the residual-gradient add inside
+    BN backward (bn_relu_bwd_add).  Off runs the kernels they replace.  A
+    captured graph keeps the setting it was captured under.  With the
+    extension loaded the answer is its launchers' own reading of the
+    variable, so the Python wiring and the kernels' routes cannot disagree;
+    the parse below serves only a machine without the extension."""
+    ext = _load()
+    if ext is not None:
+        return ext.step_fused_on()
+    return os.environ.get('HETEROFL_STEP_FUSED', '1')[:1] != '0'
+
+
 _FP8 = False
 
 

@@ -116,6 +116,25 @@ std::vector<at::Tensor> lm_head_topk(at::Tensor x, at::Tensor packed,
                                      at::Tensor vocab_mask, int64_t V,
                                      int64_t E, int64_t k, int64_t splits);
 int64_t lm_head_topk_splits(int64_t M, int64_t V);
+std::vector<at::Tensor> bn_relu_bwd_add(at::Tensor dy, at::Tensor x,
+                                        at::Tensor gamma, at::Tensor beta,
+                                        at::Tensor mean, at::Tensor invstd,
+                                        at::Tensor addend);
+std::vector<at::Tensor> head_ce_fwd(at::Tensor feat, at::Tensor w,
+                                    at::Tensor b, at::Tensor labels,
+                                    at::Tensor mask, at::Tensor metrics,
+                                    int64_t R);
+std::vector<at::Tensor> head_ce_bwd(at::Tensor up, at::Tensor scores,
+                                    at::Tensor labels, at::Tensor mask,
+                                    at::Tensor pooled, at::Tensor w,
+                                    int64_t R, int64_t H, int64_t W,
+                                    bool bf16_feat, bool want_db);
+std::string head_ce_route(int64_t N, int64_t R, int64_t C, int64_t HW,
+                          int64_t J, int64_t elem_size, bool aligned);
+bool step_fused_on();
+std::vector<at::Tensor> batch_gather(at::Tensor x_all, at::Tensor y_all,
+                                     at::Tensor counter, at::Tensor ticket,
+                                     int64_t B);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bn_relu_fwd", &bn_relu_fwd, "fused sBN+ReLU forward");
@@ -145,6 +164,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
     m.def("head_fwd", &head_fwd, "fused avgpool+per-client-linear forward");
     m.def("head_bwd", &head_bwd, "fused head backward");
+    m.def("bn_relu_bwd_add", &bn_relu_bwd_add,
+          "fused sBN+ReLU backward with dx + addend in the dx store");
+    m.def("head_ce_fwd", &head_ce_fwd,
+          "avgpool + per-client linear + masked CE (+ metrics) forward, one "
+          "launch");
+    m.def("head_ce_bwd", &head_ce_bwd,
+          "masked CE backward + head backward, one launch");
+    m.def("head_ce_route", &head_ce_route,
+          "route head_ce_fwd / head_ce_bwd would take (vec / elem / chain); "
+          "launches nothing");
+    m.def("step_fused_on", &step_fused_on,
+          "HETEROFL_STEP_FUSED as the launchers read it");
+    m.def("batch_gather", &batch_gather,
+          "copy batch `counter` of the epoch buffers and advance the counter, "
+          "one launch");
     m.def("attn_fwd", &attn_fwd, "fused small-S attention forward");
     m.def("attn_bwd", &attn_bwd, "fused small-S attention backward");
     m.def("attn_fwd_block", &attn_fwd_block,

@@ -145,11 +145,26 @@ bn_apply_relu_kernel(const T* __restrict__ x,
 // relu mask from pre = xhat*g+b; dx = invstd*g*(dym - s1/M - xhat*s2/M).
 // STAGE: the channel's x and (relu-masked) dy are kept in LDS from the
 // reduction pass so the dx pass reads LDS, not global.
-template <typename T, bool STAGE>
+// ADD (bn_relu_bwd_add): the dx store becomes round_T(float(round_T(dx)) +
+// float(addend)), the bits of a separate add of the two T tensors.
+template <typename T>
+__device__ __forceinline__ float round_T(float v) {
+    T t;
+    st_f32(&t, v);
+    return ld_f32(&t);
+}
+// a + b never contracted with the product that made a (fp32 dx: a plain add)
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+template <typename T, bool STAGE, bool ADD>
 __global__ void __launch_bounds__(256)
 bn_relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                    const float* __restrict__ gamma, const float* __restrict__ beta,
                    const float* __restrict__ mean, const float* __restrict__ invstd,
+                   const T* __restrict__ addend,
                    T* __restrict__ dx, float* __restrict__ dgamma,
                    float* __restrict__ dbeta, int N, int C, int HW) {
     const int c = blockIdx.x;
@@ -197,7 +212,11 @@ bn_relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
             const float pre = xh * g + b;
             d = pre > 0.f ? ld_f32(dy + off) : 0.f;
         }
-        st_f32(dx + off, gis * (d - k1 - xh * k2));
+        const float v = gis * (d - k1 - xh * k2);
+        if (ADD)
+            st_f32(dx + off, add_rn(round_T<T>(v), ld_f32(addend + off)));
+        else
+            st_f32(dx + off, v);
     }
 }
 
@@ -300,13 +319,14 @@ bn_relu_fwd_vec_kernel(const T* __restrict__ x,
     }
 }
 
-template <typename T>
+template <typename T, bool ADD>
 __global__ void __launch_bounds__(256)
 bn_relu_bwd_vec_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                        const float* __restrict__ gamma,
                        const float* __restrict__ beta,
                        const float* __restrict__ mean,
-                       const float* __restrict__ invstd, T* __restrict__ dx,
+                       const float* __restrict__ invstd,
+                       const T* __restrict__ addend, T* __restrict__ dx,
                        float* __restrict__ dgamma, float* __restrict__ dbeta,
                        int N, int C, int HW) {
     constexpr int V = 16 / sizeof(T);
@@ -323,6 +343,7 @@ bn_relu_bwd_vec_kernel(const T* __restrict__ dy, const T* __restrict__ x,
     const T* xc = x + (long)c * HW;
     const T* dyc = dy + (long)c * HW;
     T* dxc = dx + (long)c * HW;
+    const T* adc = ADD ? addend + (long)c * HW : nullptr;
     const float m = mean[c], is = invstd[c];
     const float g = gamma ? gamma[c] : 1.f;
     const float b = beta ? beta[c] : 0.f;
@@ -375,6 +396,13 @@ bn_relu_bwd_vec_kernel(const T* __restrict__ dy, const T* __restrict__ x,
             const float pre = xh * g + b;
             const float d = pre > 0.f ? fd[e] : 0.f;
             fd[e] = gis * (d - k1 - xh * k2);
+        }
+        if (ADD) {
+            float fa[V];
+            unpack16<T>(*(const uint4*)(adc + ww.n * samp_stride + ww.j * V),
+                        fa);
+#pragma unroll
+            for (int e = 0; e < V; ++e) fd[e] = add_rn(round_T<T>(fd[e]), fa[e]);
         }
         *(uint4*)(dxc + ww.n * samp_stride + ww.j * V) = pack16<T>(fd);
         ww.step();
@@ -602,9 +630,13 @@ std::vector<at::Tensor> bn_relu_fwd(at::Tensor x, at::Tensor gamma,
     return {y, mean, invstd};
 }
 
-std::vector<at::Tensor> bn_relu_bwd(at::Tensor dy, at::Tensor x,
-                                    at::Tensor gamma, at::Tensor beta,
-                                    at::Tensor mean, at::Tensor invstd) {
+template <bool ADD>
+static std::vector<at::Tensor> bn_relu_bwd_impl(at::Tensor dy, at::Tensor x,
+                                                at::Tensor gamma,
+                                                at::Tensor beta,
+                                                at::Tensor mean,
+                                                at::Tensor invstd,
+                                                at::Tensor addend) {
     const int N = x.size(0), C = x.size(1);
     const int HW = x.numel() / (N * C);
     auto dx = at::empty_like(x);
@@ -612,27 +644,55 @@ std::vector<at::Tensor> bn_relu_bwd(at::Tensor dy, at::Tensor x,
     auto dgamma = at::empty({C}, opts);
     auto dbeta = at::empty({C}, opts);
     auto dyc = dy.contiguous();
+    at::Tensor adc;
+    if (ADD) {
+        TORCH_CHECK(addend.is_cuda() && addend.sizes() == x.sizes() &&
+                        addend.scalar_type() == x.scalar_type(),
+                    "bn_relu_bwd_add: addend must match x");
+        adc = addend.contiguous();
+    }
     auto stream = at::hip::getCurrentHIPStream();
     const long stage_bytes = 2L * N * (x.numel() / (N * C)) * x.element_size();
     const BnRoute route = bn_route(true, N, HW, (int)x.element_size(),
                                    ptr_aligned(x.data_ptr(), 16) &&
                                        ptr_aligned(dyc.data_ptr(), 16) &&
-                                       ptr_aligned(dx.data_ptr(), 16));
+                                       ptr_aligned(dx.data_ptr(), 16) &&
+                                       (!ADD ||
+                                        ptr_aligned(adc.data_ptr(), 16)));
     const float* gp = gamma.defined() ? gamma.data_ptr<float>() : nullptr;
     const float* bp = beta.defined() ? beta.data_ptr<float>() : nullptr;
     DISPATCH_FT(x.scalar_type(), {
-        auto kern = route == BN_VEC ? bn_relu_bwd_vec_kernel<scalar_t>
-                    : route == BN_STAGED ? bn_relu_bwd_kernel<scalar_t, true>
-                                         : bn_relu_bwd_kernel<scalar_t, false>;
+        auto kern = route == BN_VEC ? bn_relu_bwd_vec_kernel<scalar_t, ADD>
+                    : route == BN_STAGED
+                        ? bn_relu_bwd_kernel<scalar_t, true, ADD>
+                        : bn_relu_bwd_kernel<scalar_t, false, ADD>;
         hipLaunchKernelGGL(kern, dim3(C), dim3(256),
                            route == BN_DIRECT ? 0 : (int)stage_bytes, stream,
                            (const scalar_t*)dyc.data_ptr(),
                            (const scalar_t*)x.data_ptr(), gp, bp,
                            mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                           ADD ? (const scalar_t*)adc.data_ptr() : nullptr,
                            (scalar_t*)dx.data_ptr(), dgamma.data_ptr<float>(),
                            dbeta.data_ptr<float>(), N, C, HW);
     });
     return {dx, dgamma, dbeta};
+}
+
+std::vector<at::Tensor> bn_relu_bwd(at::Tensor dy, at::Tensor x,
+                                    at::Tensor gamma, at::Tensor beta,
+                                    at::Tensor mean, at::Tensor invstd) {
+    return bn_relu_bwd_impl<false>(dy, x, gamma, beta, mean, invstd,
+                                   at::Tensor());
+}
+
+// bn_relu_bwd with dx + addend in the dx store (the residual branch's
+// gradient, which the autograd engine would add in a launch of its own):
+// bit-equal to bn_relu_bwd(...)[0] + addend in x's dtype, on every route.
+std::vector<at::Tensor> bn_relu_bwd_add(at::Tensor dy, at::Tensor x,
+                                        at::Tensor gamma, at::Tensor beta,
+                                        at::Tensor mean, at::Tensor invstd,
+                                        at::Tensor addend) {
+    return bn_relu_bwd_impl<true>(dy, x, gamma, beta, mean, invstd, addend);
 }
 
 std::vector<at::Tensor> gn_relu_fwd(at::Tensor x, at::Tensor gamma,

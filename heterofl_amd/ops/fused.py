@@ -48,6 +48,67 @@ def fused_norm_relu(x, weight, bias, kind, groups=1, eps=1e-5):
     return _FusedNormReLU.apply(x, weight, bias, kind, groups, eps)
 
 
+class _FusedNormReLUAlias(torch.autograd.Function):
+    """BN+ReLU that also hands its input back: (y, x_alias) = f(x).  A block
+    without a shortcut conv uses x_alias as its residual, so x has this one
+    consumer and the residual branch's gradient arrives here as dx_alias and
+    is added inside the BN backward kernel's dx store (bn_relu_bwd_add)
+    instead of by the autograd engine in a launch of its own.  The sum has
+    the bits of that separate add.  Off the GPU the same function runs in
+    torch ops (the oracle of the wiring and of gradcheck)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        ctx.set_materialize_grads(False)
+        ctx.native = use_native(x)
+        if ctx.native:
+            ext = require_native()
+            xc = x.contiguous()
+            y, mean, invstd = ext.bn_relu_fwd(xc, weight, bias, eps)
+        else:
+            xc = x
+            mean = x.mean(dim=(0, 2, 3))
+            var = x.var(dim=(0, 2, 3), unbiased=False)
+            invstd = (var + eps).rsqrt()
+            cv = (1, -1, 1, 1)
+            y = F.relu((x - mean.view(cv)) * (invstd * weight).view(cv)
+                       + bias.view(cv))
+        ctx.save_for_backward(xc, weight, bias, mean, invstd)
+        return y, x
+
+    @staticmethod
+    def backward(ctx, dy, dalias):
+        x, weight, bias, mean, invstd = ctx.saved_tensors
+        if dy is None:
+            dy = torch.zeros_like(x)
+        if ctx.native:
+            ext = require_native()
+            if dalias is None:
+                dx, dgamma, dbeta = ext.bn_relu_bwd(dy, x, weight, bias, mean,
+                                                    invstd)
+            else:
+                dx, dgamma, dbeta = ext.bn_relu_bwd_add(
+                    dy, x, weight, bias, mean, invstd, dalias.to(x.dtype))
+            return dx, dgamma, dbeta, None
+        cv = (1, -1, 1, 1)
+        M = x.numel() // x.size(1)
+        xh = (x - mean.view(cv)) * invstd.view(cv)
+        pre = xh * weight.view(cv) + bias.view(cv)
+        d = torch.where(pre > 0, dy, torch.zeros_like(dy))
+        dbeta = d.sum((0, 2, 3))
+        dgamma = (d * xh).sum((0, 2, 3))
+        dx = (weight * invstd).view(cv) * (d - (dbeta / M).view(cv)
+                                           - xh * (dgamma / M).view(cv))
+        if dalias is not None:
+            dx = dx + dalias
+        return dx, dgamma, dbeta, None
+
+
+def fused_norm_relu_alias(x, weight, bias, eps=1e-5):
+    """(relu(bn(x) * w + b), x_alias): see _FusedNormReLUAlias."""
+    return _FusedNormReLUAlias.apply(x, weight, bias, eps)
+
+
 def bn_relu_route(direction, N, C, HW, elem_size, aligned=True):
     """Route bn_relu_fwd / bn_relu_bwd (direction 'fwd' / 'bwd') take for an
     (N, C, HW) tensor of elem_size bytes per element; the launchers' own rule,
@@ -488,6 +549,81 @@ class _FusedHead(torch.autograd.Function):
 
 def fused_head(feat, weight, bias, R):
     return _FusedHead.apply(feat, weight, bias, R)
+
+
+class _FusedHeadCE(torch.autograd.Function):
+    """The vision step's classifier tail, one launch each way
+    (ops/csrc/head_ce.hip): avg-pool + per-client linear + masked CE with the
+    device-side metrics forward; masked-CE backward + head backward.  Returns
+    (losses (R,), scores (N, R, J)); only losses carries a gradient.  Outside
+    the kernels' envelope (head_ce_route 'chain') the entries run
+    head_fwd -> masked_ce_fwd and masked_ce_bwd -> head_bwd themselves."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, bias, labels, mask, metrics, R):
+        ext = require_native()
+        feat = feat.contiguous()
+        none = torch.Tensor()
+        labels = labels.contiguous()
+        losses, pooled, scores = ext.head_ce_fwd(
+            feat, weight, bias if bias is not None else none, labels,
+            mask if mask is not None else none,
+            metrics if metrics is not None else none, R)
+        ctx.save_for_backward(scores, labels,
+                              mask if mask is not None else none, pooled,
+                              weight)
+        ctx.meta = (R, feat.size(2), feat.size(3),
+                    feat.dtype == torch.bfloat16, bias is not None,
+                    mask is not None)
+        ctx.mark_non_differentiable(scores)
+        return losses, scores
+
+    @staticmethod
+    def backward(ctx, up, _dscores):
+        ext = require_native()
+        scores, labels, mask, pooled, weight = ctx.saved_tensors
+        R, H, W, bf16_feat, has_bias, has_mask = ctx.meta
+        # up goes in as it comes: the kernel reads it through its stride
+        dw, db, dfeat = ext.head_ce_bwd(
+            up, scores, labels, mask if has_mask else torch.Tensor(), pooled,
+            weight, R, H, W, bf16_feat, has_bias)
+        return (dfeat, dw, (db if has_bias else None), None, None, None,
+                None)
+
+
+def fused_head_ce(feat, weight, bias, labels, mask, R, metrics=None):
+    """feat (N, R*C, H, W) -> (losses (R,), scores (N, R, J)): pool, per-client
+    linear and masked CE.  On the GPU the two-launch kernels; elsewhere today's
+    functions composed (fused_head's torch twin and batched_masked_ce)."""
+    if use_native(feat):
+        return _FusedHeadCE.apply(feat, weight, bias, labels, mask, metrics,
+                                  R)
+    from ..fed.batched import batched_masked_ce
+    pooled = F.adaptive_avg_pool2d(feat, 1).view(feat.size(0), R, -1)
+    scores = torch.einsum('nri,roi->nro', pooled, weight)
+    if bias is not None:
+        scores = scores + bias
+    losses = batched_masked_ce(scores.float(), labels, mask, metrics=metrics)
+    return losses, scores
+
+
+def head_ce_route(N, R, C, HW, J, elem_size, aligned=True):
+    """Route head_ce_fwd / head_ce_bwd take: 'vec' (16-byte feat / dfeat
+    accesses: HW * elem_size a multiple of 16, aligned bases), 'elem', or
+    'chain' (the old four kernels: HETEROFL_STEP_FUSED=0, or an LDS stage
+    over 64 KB: forward ((N + J) * (C + 1) + N * J) * 4 bytes, backward
+    (N * J + 32 * J) * 4).  Launches nothing."""
+    ext = require_native()
+    return ext.head_ce_route(N, R, C, HW, J, elem_size, aligned)
+
+
+def batch_gather(x_all, y_all, counter, B, ticket):
+    """(x_all[c*B:(c+1)*B], y_all[c*B:(c+1)*B]) for c = counter[0], in one
+    launch that also leaves counter at c + 1 (ops/csrc/batch_gather.hip).
+    ticket: an int32 cell holding 0, back at 0 afterwards."""
+    ext = require_native()
+    xb, yb = ext.batch_gather(x_all, y_all, counter, ticket, B)
+    return xb, yb
 
 
 class GraphClipSGD:

@@ -5,8 +5,11 @@ the same either way, so on - off is the reduce's) and clip+SGD.  Every row is
 timed with the switch off and on, alternating, in one process, with hip
 events: as replays of two captured graphs of `iters` launches each (the
 flagship runs captured graphs, and eager launches floor near 6 us each, above
-most of these kernels), or with --eager as plain launches.  Run on a GPU box:
-    python scripts/streambench.py [iters] [reps] [--eager]
+most of these kernels), or with --eager as plain launches.  --step times the
+vision step's glue behind HETEROFL_STEP_FUSED instead: the old launch chains
+(classifier tail at both widths, batch fetch, BN backward + residual add)
+against the entries that replace them.  Run on a GPU box:
+    python scripts/streambench.py [iters] [reps] [--eager] [--step]
 """
 import os
 import sys
@@ -113,11 +116,142 @@ def row(name, off, on, note=''):
     return to, tn
 
 
+def time_pair(fn_off, fn_on, iters, reps):
+    """two different call chains instead of one call under a switch; fn_on
+    None (a build without the new entry): the chain alone, twice"""
+    if fn_on is None:
+        fn_on = fn_off
+    if EAGER:
+        off, on = [], []
+        for _ in range(reps):
+            off.append(timeit(fn_off, iters))
+            on.append(timeit(fn_on, iters))
+        return off, on
+    g_off = capture(fn_off, iters)
+    g_on = capture(fn_on, iters)
+    off, on = [], []
+    for _ in range(reps):
+        off.append(time_replay(g_off, iters))
+        on.append(time_replay(g_on, iters))
+    return off, on
+
+
+def step_rows(ext, iters, reps):
+    """The vision step's glue behind HETEROFL_STEP_FUSED, old chain (off)
+    against the new entry (on): the classifier tail at both widths, the batch
+    fetch, BN backward + residual-gradient add at the four flagship planes.
+    On a build without the new entries both columns are the old chain."""
+    from heterofl_amd.ops import fused
+    dt = torch.bfloat16
+    J = 10
+    has = hasattr(ext, 'head_ce_fwd')
+    print(f'toggle: old chain / new entry ({"present" if has else "absent"}); '
+          f'{"eager" if EAGER else "graph replay"}; {reps} repeats of '
+          f'{iters} chains, median us')
+    print(f'{"row":26} {"off_us":>8} {"on_us":>8} {"on/off":>6} '
+          f'{"off_spread":>10} {"on_spread":>9}')
+    for C in (512, 32):
+        feat = torch.randn(N, R * C, 4, 4, device='cuda').to(dt) \
+            .requires_grad_()
+        w = (torch.randn(R, J, C, device='cuda') / C ** 0.5).requires_grad_()
+        b = torch.randn(R, J, device='cuda').requires_grad_()
+        y = torch.randint(0, J, (N, R), device='cuda')
+        mask = (torch.rand(R, J, device='cuda') > 0.4).float()
+        metrics = torch.zeros(R, 3, device='cuda')
+        ones = torch.ones(R, device='cuda')
+
+        def chain():
+            scores = fused.fused_head(feat, w, b, R)
+            losses = fused.fused_masked_ce(scores.float(), y, mask, metrics)
+            return torch.autograd.grad(losses.sum(), [feat, w, b])
+
+        def entry():
+            losses, _ = fused.fused_head_ce(feat, w, b, y, mask, R,
+                                            metrics=metrics)
+            return torch.autograd.grad(losses, [feat, w, b],
+                                       grad_outputs=ones)
+
+        off, on = time_pair(chain, entry if has else None, iters, reps)
+        row(f'head+CE tail C={C}', off, on, '7 launches -> 2')
+
+    B = 10
+    cap = (iters + 4) * B
+    x_all = torch.randn(cap, R * 3, 32, 32, device='cuda').to(dt)
+    y_all = torch.randint(0, J, (cap, R), device='cuda')
+    counter = torch.zeros(1, dtype=torch.long, device='cuda')
+    ticket = torch.zeros(1, dtype=torch.int32, device='cuda')
+    arange = torch.arange(B, device='cuda')
+    calls = [0]
+
+    def rewind():
+        # first call of every `iters`: the counter back to 0, so a replay
+        # never walks off the buffer (one more launch per `iters` chains)
+        if calls[0] % iters == 0:
+            counter.zero_()
+        calls[0] += 1
+
+    def fetch5():
+        rewind()
+        idx = counter * B + arange
+        xb = x_all.index_select(0, idx)
+        yb = y_all.index_select(0, idx)
+        counter.add_(1)
+        return xb, yb
+
+    def fetch1():
+        rewind()
+        return fused.batch_gather(x_all, y_all, counter, B, ticket)
+
+    # like capture(), with the call count set so that the recorded graph
+    # starts with the rewind
+    off, on = [], []
+    for fn, dst in ((fetch5, off), (fetch1 if has else fetch5, on)):
+        if EAGER:
+            calls[0] = 0
+            dst.extend(timeit(fn, iters) for _ in range(reps))
+            continue
+        for _ in range(3):
+            calls[0] = 1
+            counter.zero_()
+            fn()
+        torch.cuda.synchronize()
+        calls[0] = 0
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(iters):
+                fn()
+        g.replay()
+        torch.cuda.synchronize()
+        dst.extend(time_replay(g, iters) for _ in range(reps))
+    # interleaving is lost here (one graph after the other); spreads say
+    # whether that matters
+    row('batch fetch B=10', off, on, '5 launches -> 1')
+
+    for div in (1, 16):
+        for H, width in zip(PLANES, HIDDEN):
+            C = R * width // div
+            x = torch.randn(N, C, H, H, device='cuda').to(dt)
+            dy = torch.randn(N, C, H, H, device='cuda').to(dt)
+            ad = torch.randn(N, C, H, H, device='cuda').to(dt)
+            g = torch.rand(C, device='cuda') + 0.5
+            bb = torch.randn(C, device='cuda')
+            _, mean, invstd = ext.bn_relu_fwd(x, g, bb, 1e-5)
+            route = fused.bn_relu_route('bwd', N, C, H * H, 2)
+            off, on = time_pair(
+                lambda: ext.bn_relu_bwd(dy, x, g, bb, mean, invstd)[0] + ad,
+                (lambda: ext.bn_relu_bwd_add(dy, x, g, bb, mean, invstd, ad))
+                if has else None, iters, reps)
+            row(f'bn bwd+add {H}x{H} C={C}', off, on, route)
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     iters = int(args[0]) if len(args) > 0 else 50
     reps = int(args[1]) if len(args) > 1 else 5
     ext = require_native()
+    if '--step' in sys.argv:
+        step_rows(ext, iters, reps)
+        return
     from heterofl_amd.ops.fused import (FusedClipSGD, bn_relu_route,
                                         conv_plan)
     dt = torch.bfloat16
